@@ -9,6 +9,9 @@ DESIGN.md, never as `value`).  Workloads (config.workload):
   crc      BASELINE configs[1]: 1 GiB segment, CRC32C only
 N > 1: one process per GPU (torch.distributed.run), segments sharded segment-major, no data-path collective
  — weak scaling: every GPU gets the same number of segments.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times --steps steps and prints the line; --full adds every leg outside the timed region (oracle check,
+inverse chain, sustained / mixed-load / value_B / CPU-baseline / end-to-end / configs legs, line-rate probe).  --dump-outputs DIR writes
+what the last timed step returned (dump_outputs).
 """
 import argparse
 import subprocess
@@ -40,7 +43,7 @@ except (OSError, FileNotFoundError):
             tempfile.tempdir = None
             break
 GiB = float(1 << 30)
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s peak
+HBM_PEAK_GBS = 8000.0          # MI355X: HBM3E 8.0 TB/s peak
 
 
 def parse():
@@ -89,6 +92,13 @@ def parse():
     ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE configs[1] / configs[2] legs (CRC32C only; AES-256-GCM + CRC32C on one 1 GiB segment)")
     ap.add_argument("--settle-seconds", type=float, default=10.0,
                     help="idle time between the broker-shaped children (which saturate the chip for ~100 s) and this process's own measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the timed steps: the line-rate probe, the oracle check, the inverse chain, the sustained, mixed-load, "
+                         "value_B, CPU-baseline, end-to-end, broker and configs[1] / configs[2] legs (each still subject to its --no-* switch).  Without it "
+                         "a run sets up, warms up, times --steps steps and prints the line, whose other legs are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned to its caller as DIR/<name>.npy (float64 / float32, about 17 MB): "
+                         "status, dst_len and crc32c of every chunk, the last 16 bytes of every transformed chunk and a seeded sample of 4 Mi transformed bytes")
     return ap.parse_args()
 
 
@@ -199,6 +209,32 @@ def _device_state_under_load(out, after_s):
         out["error"] = repr(e)[:160]
 
 
+DUMP_SAMPLE = 1 << 22                                      # transformed bytes sampled by --dump-outputs (16 MiB as float32)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, desc, take, transformed):
+    """--dump-outputs: what the caller of the timed path received from its last step, as float arrays - the batch's descriptors (status,
+    transformed size and CRC32C of every chunk) and, when the step wrote transformed chunks, the last 16 bytes of each (the GCM tag when
+    encrypting: it covers the whole chunk) and the bytes at DUMP_SAMPLE positions drawn with a fixed seed over the transformed chunks.
+    `take(idx)` returns the output buffer's bytes at the int64 byte positions `idx` as a uint8 numpy array."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"status": desc["status"].astype(np.float64), "crc32c": desc["crc32c"].astype(np.float64)}
+    if transformed and desc.size:
+        lens = desc["dst_len"].astype(np.int64)
+        offs = desc["dst_off"].astype(np.int64)
+        arrays["dst_len"] = lens.astype(np.float64)
+        tail = offs[:, None] + np.clip(lens[:, None] - 16 + np.arange(16), 0, None)
+        arrays["tail16"] = take(tail.reshape(-1)).reshape(-1, 16).astype(np.float32)
+        rng = np.random.default_rng(DUMP_SEED)
+        k = min(DUMP_SAMPLE, int(lens.sum()))
+        which = rng.integers(0, desc.size, k)
+        pos = offs[which] + (rng.random(k) * lens[which]).astype(np.int64)
+        arrays["sample"] = take(pos).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -212,7 +248,7 @@ def main():
         raise SystemExit("bench.py: --gpus %d but the launcher started %d rank(s) (WORLD_SIZE): the line would misreport n_gpus" % (args.gpus, world))
     # the broker-shaped leg of end_to_end comes FIRST, in children, while this process has not initialised HIP yet (see broker_leg_first)
     broker_first = None
-    if (rank == 0 and world == 1 and not args.rehearse and args.workload in ("auto", "full") and not args.no_broker and not args.no_end_to_end
+    if (args.full and rank == 0 and world == 1 and not args.rehearse and args.workload in ("auto", "full") and not args.no_broker and not args.no_end_to_end
             and not args.broker_inprocess and args.inflight > 1 and args.steps > 1 and not args.split_segments):
         broker_first = broker_leg_first(args)
         time.sleep(max(0.0, args.settle_seconds))                        # the children kept the chip saturated: let it idle before the timed region
@@ -271,6 +307,9 @@ def main():
         @staticmethod
         def equal(a, b):
             return bool(np.array_equal(a, b)) if rehearse else bool(torch.equal(a, b))
+        @staticmethod
+        def take(b, idx):
+            return b[idx] if rehearse else b[torch.from_numpy(idx).to(dev)].cpu().numpy()
         @staticmethod
         def sync():
             if not rehearse:
@@ -359,7 +398,7 @@ def main():
     # do nothing but touch random 64-B lines of 768 KiB tables in the workspace layout, reads : rewrites : blind stores as the compressor's PMC
     # passes count them.  roofline.binding_resource.peak below is this number - same box, same minute - not a band from an older box.
     line_rate = None
-    if rank == 0 and world == 1 and workload == "full" and not rehearse and not args.no_line_rate_probe:
+    if args.full and rank == 0 and world == 1 and workload == "full" and not rehearse and not args.no_line_rate_probe:
         exe = os.path.join(ROOT, "tools", "ubench", "line_rate")
         if not os.path.exists(exe):
             subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tools", "ubench"), "line_rate"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
@@ -415,9 +454,12 @@ def main():
         svc.update({k: svc1[k] for k in ("waves", "compute_units", "cu_keys_seen", "reserved_cus")})
     for t in range(1, T):
         assert (ds[t]["status"] == 0).all() and (ds[t]["dst_len"] == d["dst_len"]).all() and (ds[t]["crc32c"] == d["crc32c"]).all()
+    if args.dump_outputs and rank == 0:
+        tl = (args.steps - 1) % T                        # the caller that ran the last timed step
+        dump_outputs(args.dump_outputs, ds[tl], lambda idx: Mem.take(dsts[tl], idx), workload != "crc")
     # for the record (outside the timed region): the same batch strictly one at a time
     single = None
-    if T > 1:
+    if args.full and T > 1:
         fence()
         t1 = time.perf_counter()
         for _ in range(2):
@@ -431,7 +473,7 @@ def main():
     # (batches completed) over time across the middle 60 % of the run, i.e. without the ramp at either end.
     sustained = None
     box_state = {}
-    if rank == 0 and world == 1 and workload == "full" and T > 1 and not split and not args.no_sustained:
+    if args.full and rank == 0 and world == 1 and workload == "full" and T > 1 and not split and not args.no_sustained:
         TS, BS, stag = (5, 10, 0.25) if not rehearse else (5, 3, 0.01)
         nbytes = (lambda b: b.size) if rehearse else (lambda b: b.numel())
         xctx = [N.ctx_create(0, n, CH) for _ in range(TS - T)]
@@ -479,7 +521,7 @@ def main():
     # timed region's callers go on submitting their batches (more chunks queued than the chip holds) while this thread restores 1 and 4
     # chunks host -> host through a context of its own.  The compressor service leaves `reserved_cus` compute units alone for exactly this.
     mixed = None
-    if rank == 0 and world == 1 and workload == "full" and T > 1 and not split and not args.no_mixed_load and not rehearse and n >= 4:
+    if args.full and rank == 0 and world == 1 and workload == "full" and T > 1 and not split and not args.no_mixed_load and not rehearse and n >= 4:
         try:
             hfr = dst[:4 * slot].cpu().numpy(); hbk = np.zeros(4 * CH, np.uint8)
             N.host_register(hfr); N.host_register(hbk)
@@ -547,7 +589,7 @@ def main():
     # ---- the same chain on Kafka-shaped BINARY content (never `value`): v2 record batches, tsxform/synth.py "B" ------------------------
     # How far does K's number carry?  Sequence density sets the GiB/s; B has binary headers, varint framing and incompressible payloads.
     value_b = None
-    if rank == 0 and world == 1 and workload == "full" and T > 1 and not split and not args.no_value_b and args.dist == "K" and (n >= 256 or rehearse):
+    if args.full and rank == 0 and world == 1 and workload == "full" and T > 1 and not split and not args.no_value_b and args.dist == "K" and (n >= 256 or rehearse):
         try:
             import multiprocessing as mp
             from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
@@ -626,7 +668,7 @@ def main():
 
     # ---- parity spot-check against the oracle (outside the timed region) ------------------------------
     verified = None
-    if rank == 0 and not args.no_verify:
+    if args.full and rank == 0 and not args.no_verify:
         from concurrent.futures import ThreadPoolExecutor
         from oracle import oracle as o
         # EVERY chunk of the timed batch (--verify-chunks k: k of them, spread over the batch): CRC32C and transformed bytes against
@@ -658,7 +700,7 @@ def main():
     # tsx_detransform_batch over the batch just produced (GCM tag check + decrypt, Zstd frame decode, CRC32C of the restored
     # bytes), device resident like the forward step; restored bytes must equal the source segment byte for byte.
     inverse = None
-    if workload != "crc" and not args.no_inverse:
+    if args.full and workload != "crc" and not args.no_inverse:
         back = Mem.empty(max(n, 1) * CH)
         e = np.zeros(n, nat.DESC_DTYPE)
         e["src_off"] = d["dst_off"]; e["src_len"] = d["dst_len"]; e["iv"] = d["iv"]
@@ -804,7 +846,7 @@ def main():
     # (T = 1 is the per-thread rate of the reference's chain, T = 10 the reference's default RLM copier pool, "all" what the
     # box could do if every core ran uploads).  The headline object is the all-cores leg.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not rehearse:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not rehearse:
         from oracle import oracle as o
         cores = usable_cores()
         try:
@@ -883,7 +925,7 @@ def main():
     # ---- end to end: the same batch host -> host through TSX_MEM_HOST / TSX_MEM_HOST_PACKED (what the JNI shim uses), PCIe included.
     # Never `value`.  Pageable buffers first (the runtime stages them), then the same buffers pinned with tsx_host_register.
     e2e = None
-    if rank == 0 and world == 1 and workload != "crc" and not args.no_end_to_end and not rehearse:
+    if args.full and rank == 0 and world == 1 and workload != "crc" and not args.no_end_to_end and not rehearse:
         PCIE = 64.0                                                       # GB/s per direction, PCIe 5.0 x16
         hsrc = src.cpu().numpy()
         hdst = np.zeros(n * slot, np.uint8)
@@ -1026,7 +1068,7 @@ def main():
     # ---- BASELINE configs[1] and configs[2] on one 1 GiB segment (never `value`): CRC32C only; AES-256-GCM + CRC32C - what a broker runs
     # whenever the producers compress (RemoteStorageManager.java:381-398 leaves Zstd out then, EncryptionChunkEnumeration.java:66-84) ----
     configs = None
-    if rank == 0 and world == 1 and workload == "full" and not rehearse and not args.no_configs and n >= 256:
+    if args.full and rank == 0 and world == 1 and workload == "full" and not rehearse and not args.no_configs and n >= 256:
         configs = {}
         m = 256
         from oracle import oracle as o

@@ -23,7 +23,7 @@ def _free_port():
 def _launch(world, extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--rehearse", "--backend", "gloo", "--workload", "full"] + extra
+           "--rehearse", "--backend", "gloo", "--workload", "full", "--full"] + extra
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -55,7 +55,7 @@ def test_gpus_2_without_a_launcher_starts_two_ranks(emu, oracle):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rehearse", "--backend", "gloo",
-           "--workload", "full", "--chunk-bytes", "20000", "--chunks-per-segment", "3", "--segments", "2", "--inflight", "2"]
+           "--workload", "full", "--full", "--chunk-bytes", "20000", "--chunks-per-segment", "3", "--segments", "2", "--inflight", "2"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -93,7 +93,7 @@ def test_single_rank_line_has_every_leg(emu, oracle):
     if not oracle.zstd_version().startswith("1.5.7"):
         pytest.skip("libzstd 1.5.7 not available")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--rehearse", "--backend", "gloo",
-           "--chunk-bytes", "8192", "--chunks-per-segment", "3", "--segments", "2"]
+           "--chunk-bytes", "8192", "--chunks-per-segment", "3", "--segments", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -105,6 +105,51 @@ def test_single_rank_line_has_every_leg(emu, oracle):
     assert j["detransform"]["round_trip_exact"] is True and j["roofline"]["bound"] == "hbm"
     assert j["value_B"]["exact_vs_oracle"] is True and j["value_B"]["batches"] == 8 and j["value_B"]["value"] > 0, j["value_B"]
     assert j["value_B"]["value_B_1_5_6"]["exact_vs_oracle"] is True and j["value_B"]["value_B_1_5_6"]["value"] > 0, j["value_B"]      # the profile a zstd-jni 1.5.6 broker selects
+
+
+def test_plain_run_times_the_steps_only_and_dumps_the_last_step(emu, oracle, tmp_path):
+    """Without --full the line carries the timed steps alone (every other leg null); --dump-outputs writes what the last step returned:
+    status / dst_len / crc32c of every chunk, the last 16 bytes of every transformed chunk and a seeded sample of its bytes - the same
+    files from run to run, and the chunks the oracle makes from the same inputs."""
+    if not oracle.zstd_version().startswith("1.5.7"):
+        pytest.skip("libzstd 1.5.7 not available")
+    from tsxform import synth
+    CH, cps, nseg = 8192, 3, 2
+    outs = []
+    for k in range(2):
+        out = tmp_path / ("out%d" % k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--rehearse", "--backend", "gloo",
+               "--chunk-bytes", str(CH), "--chunks-per-segment", str(cps), "--segments", str(nseg), "--inflight", "2", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="1"))
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["unit"] == "GiB/s" and j["higher_is_better"] is True and j["dtype"] == "u8"
+        for leg in ("cpu_baseline", "sustained", "value_B", "mixed_load", "configs", "end_to_end", "detransform"):
+            assert j[leg] is None, leg
+        assert j["config"]["verified_chunks_vs_oracle"] is None and j["config"]["gibs_one_batch_at_a_time"] is None
+        outs.append({f[:-4]: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))})
+    a, b = outs
+    assert sorted(a) == ["crc32c", "dst_len", "sample", "status", "tail16"]
+    assert all(a[k].dtype in (np.float32, np.float64) for k in a) and sum(a[k].nbytes for k in a) <= 64 << 20
+    assert all(np.array_equal(a[k], b[k]) for k in a)                 # identical inputs, identical outputs
+    n = nseg * cps
+    of = oracle.COMPRESS | oracle.ENCRYPT
+    exp = [oracle.transform_chunk(of, synth.KEY, synth.AAD, synth.iv_for(s, c), synth.gen_chunk("K", 1000 + s, s, c, CH).tobytes())[0]
+           for s in range(nseg) for c in range(cps)]
+    assert (a["status"] == 0).all() and a["dst_len"].tolist() == [len(e) for e in exp]
+    assert a["crc32c"].tolist() == [oracle.crc32c(synth.gen_chunk("K", 1000 + s, s, c, CH)) for s in range(nseg) for c in range(cps)]
+    assert a["tail16"].shape == (n, 16) and all(bytes(a["tail16"][i].astype(np.uint8)) == exp[i][-16:] for i in range(n))
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
+    bm = importlib.util.module_from_spec(spec); spec.loader.exec_module(bm)
+    lens = np.array([len(e) for e in exp], np.int64)
+    k = min(bm.DUMP_SAMPLE, int(lens.sum()))
+    rng = np.random.default_rng(bm.DUMP_SEED)
+    which = rng.integers(0, n, k)
+    at = (rng.random(k) * lens[which]).astype(np.int64)
+    assert a["sample"].tolist() == [exp[w][o] for w, o in zip(which.tolist(), at.tolist())]
 
 
 def test_broker_leg_runs_without_torch_and_checks_sizes(emu, tmp_path):
@@ -143,7 +188,7 @@ def test_broker_leg_runs_without_torch_and_checks_sizes(emu, tmp_path):
 def _force_dist_cmd(extra):
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
             "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--split-segments", "--gather-object",
-            "--segments", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-sustained", "--no-end-to-end"] + extra
+            "--segments", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-sustained", "--no-end-to-end"] + extra
 
 
 def test_force_dist_runs_the_collectives_with_one_rank(emu, oracle):

@@ -25,7 +25,7 @@ def _free_port():
 def test_rccl_collectives_run_on_one_gpu(gpu, oracle):
     cmd = ["timeout", "420", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--split-segments", "--gather-object",
-           "--segments", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-sustained", "--no-end-to-end", "--verify-chunks", "4"]
+           "--segments", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-sustained", "--no-end-to-end", "--verify-chunks", "4"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
