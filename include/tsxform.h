@@ -101,7 +101,9 @@ typedef struct tsx_batch_params {
     uint32_t aad_len;      /* reference: 32                                                         */
     uint8_t  key[32];      /* AES-256 data key (SecretKey.getEncoded())                             */
     uint8_t  aad[64];
-    int32_t  zstd_level;   /* 0 = library default (3), what the reference uses; only 3 is implemented */
+    int32_t  zstd_level;   /* 0 = library default (3), what the reference uses; 1, 2, 3 are implemented (frames byte for byte
+                            * libzstd's at that level); anything else is TSX_E_UNSUPPORTED.  Members of different levels share the
+                            * device's compressor service; tsx_transformed_bound does not depend on the level                    */
     uint32_t zstd_profile; /* TSX_ZSTD_PROFILE_*                                                    */
 } tsx_batch_params;
 
@@ -126,7 +128,7 @@ typedef struct tsx_timing {
 
 /* ---- library lifetime ---------------------------------------------------------------------- */
 uint32_t    tsx_abi_version(void);
-const char* tsx_version(void);           /* "tsxform x.y (gfx950; zstd parity target 1.5.7/1.5.6 L3)" */
+const char* tsx_version(void);           /* "tsxform x.y (gfx950; zstd parity target 1.5.7/1.5.6, levels 1-3)" */
 const char* tsx_strerror(int code);
 /* device_ids == NULL: use devices 0..device_count-1; device_count <= 0: all visible devices.  An id may be listed more than once
  * (the same GPU as several logical devices, each with its own pools and compressor service: tests of the multi-device dispatch).

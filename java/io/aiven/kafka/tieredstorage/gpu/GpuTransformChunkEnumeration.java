@@ -35,6 +35,7 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
     private final int batchChunks;
     private final SecureRandom random;
     private final int zstdProfile;
+    private final int zstdLevel;             // 0: the library default (3)
     private final int device;
     private final Integer transformedChunkSize;
     private final ArrayDeque<byte[]> ready = new ArrayDeque<>();
@@ -78,7 +79,22 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
                                         final DataKeyAndAAD keyAndAad, final int batchChunks,
                                         final SecureRandom random, final int zstdProfile, final int segmentHash,
                                         final boolean readAhead) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, readAhead, 0);
+    }
+
+    /**
+     * @param zstdLevel Zstandard level of the frames, plugin configuration key {@code compression.zstd.level} (INTEGRATION.md 2):
+     *                  1, 2 or 3, or 0 for the library default (3, what the reference's zstd-jni call uses)
+     */
+    public GpuTransformChunkEnumeration(final TransformChunkEnumeration inner, final boolean compress,
+                                        final DataKeyAndAAD keyAndAad, final int batchChunks,
+                                        final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                        final boolean readAhead, final int zstdLevel) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
+        if (zstdLevel < 0 || zstdLevel > 3) {
+            throw new IllegalArgumentException("Zstd level must be 1, 2 or 3 (0: library default), " + zstdLevel + " given");
+        }
+        this.zstdLevel = zstdLevel;
         this.compress = compress;
         this.keyAndAad = keyAndAad;
         this.batchChunks = batchChunks;
@@ -209,7 +225,10 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
         final byte[] key = keyAndAad != null ? keyAndAad.dataKey.getEncoded() : null;   // a copy (SecretKeySpec.getEncoded clones)
         final int rc;
         try {
-            rc = TsxNative.transformBatch(flags, key, keyAndAad != null ? keyAndAad.aad : null, zstdProfile, descs, in.size(), src, dst);
+            rc = zstdLevel == 0
+                ? TsxNative.transformBatch(flags, key, keyAndAad != null ? keyAndAad.aad : null, zstdProfile, descs, in.size(), src, dst)
+                : TsxNative.transformBatchLevel(flags, key, keyAndAad != null ? keyAndAad.aad : null, zstdProfile, zstdLevel,
+                    descs, in.size(), src, dst);
         } finally {
             if (key != null) {
                 Arrays.fill(key, (byte) 0);            // the copy does not wait for the garbage collector

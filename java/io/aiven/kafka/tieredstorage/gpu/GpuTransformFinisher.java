@@ -120,6 +120,7 @@ public class GpuTransformFinisher {
     private final int batchChunks;
     private final SecureRandom random;
     private final int zstdProfile;
+    private final int zstdLevel;             // 0: the library default (3)
     private final int device;
     private final boolean readAhead;
     private final Bucket rateLimitingBucket;
@@ -144,7 +145,23 @@ public class GpuTransformFinisher {
                                 final int batchChunks, final SecureRandom random, final int zstdProfile, final int segmentHash,
                                 final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
                                 final boolean readAhead) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, originalFileSize, chunkingEnabled,
+            rateLimitingBucket, readAhead, 0);
+    }
+
+    /**
+     * @param zstdLevel Zstandard level of the frames, plugin configuration key {@code compression.zstd.level} (INTEGRATION.md 2):
+     *                  1, 2 or 3, or 0 for the library default (3, what the reference's zstd-jni call uses)
+     */
+    public GpuTransformFinisher(final TransformChunkEnumeration inner, final boolean compress, final DataKeyAndAAD keyAndAad,
+                                final int batchChunks, final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
+                                final boolean readAhead, final int zstdLevel) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
+        if (zstdLevel < 0 || zstdLevel > 3) {
+            throw new IllegalArgumentException("Zstd level must be 1, 2 or 3 (0: library default), " + zstdLevel + " given");
+        }
+        this.zstdLevel = zstdLevel;
         if (originalFileSize < 0) {
             throw new IllegalArgumentException("originalFileSize must be non-negative, " + originalFileSize + " given");
         }
@@ -351,7 +368,10 @@ public class GpuTransformFinisher {
         final byte[] key = keyAndAad != null ? keyAndAad.dataKey.getEncoded() : null;   // a copy (SecretKeySpec.getEncoded clones)
         final int rc;
         try {
-            rc = TsxNative.transformBatchPacked(flags, key, keyAndAad != null ? keyAndAad.aad : null, zstdProfile, descs, in.size(), src, object);
+            rc = zstdLevel == 0
+                ? TsxNative.transformBatchPacked(flags, key, keyAndAad != null ? keyAndAad.aad : null, zstdProfile, descs, in.size(), src, object)
+                : TsxNative.transformBatchPackedLevel(flags, key, keyAndAad != null ? keyAndAad.aad : null, zstdProfile, zstdLevel,
+                    descs, in.size(), src, object);
         } finally {
             if (key != null) {
                 Arrays.fill(key, (byte) 0);            // the copy does not wait for the garbage collector

@@ -151,6 +151,17 @@ public final class TsxNative {
     public static native int transformBatchPacked(int flags, byte[] key, byte[] aad, int zstdProfile,
                                                   ByteBuffer descs, int n, ByteBuffer src, ByteBuffer dst);
 
+    /**
+     * {@link #transformBatch} and {@link #transformBatchPacked} at a Zstandard level ({@code compression.zstd.level}): 1, 2 or 3, or 0
+     * for the library default (3, what the reference's zstd-jni call uses).  Any other level returns TSX_E_UNSUPPORTED, as does a
+     * library older than these methods for 1 and 2.
+     */
+    public static native int transformBatchLevel(int flags, byte[] key, byte[] aad, int zstdProfile, int zstdLevel,
+                                                 ByteBuffer descs, int n, ByteBuffer src, ByteBuffer dst);
+
+    public static native int transformBatchPackedLevel(int flags, byte[] key, byte[] aad, int zstdProfile, int zstdLevel,
+                                                       ByteBuffer descs, int n, ByteBuffer src, ByteBuffer dst);
+
     public static native int detransformBatch(int flags, byte[] key, byte[] aad,
                                               ByteBuffer descs, int n, ByteBuffer src, ByteBuffer dst);
 }

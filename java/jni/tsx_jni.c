@@ -56,10 +56,10 @@ JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_hostUnreg
     return p ? tsx_host_unregister(p) : TSX_E_INVAL;
 }
 
-static int fill_params(JNIEnv* env, tsx_batch_params* p, jint flags, jbyteArray key, jbyteArray aad, jint profile) {
+static int fill_params(JNIEnv* env, tsx_batch_params* p, jint flags, jbyteArray key, jbyteArray aad, jint profile, jint level) {
     memset(p, 0, sizeof *p);
     p->flags = (uint32_t)flags;
-    p->zstd_level = 0;                    /* library default = 3: CompressionChunkEnumeration.java:52 never sets a level */
+    p->zstd_level = (int32_t)level;       /* 0 = library default = 3: CompressionChunkEnumeration.java:52 never sets a level */
     p->zstd_profile = (uint32_t)profile;
     if (flags & TSX_ENCRYPT) {
         if (!key || (*env)->GetArrayLength(env, key) != 32) return TSX_E_INVAL;
@@ -74,10 +74,10 @@ static int fill_params(JNIEnv* env, tsx_batch_params* p, jint flags, jbyteArray 
     return TSX_OK;
 }
 
-static jint run(JNIEnv* env, int detransform, int mem_kind, jint flags, jbyteArray key, jbyteArray aad, jint profile,
+static jint run(JNIEnv* env, int detransform, int mem_kind, jint flags, jbyteArray key, jbyteArray aad, jint profile, jint level,
                 jobject descs, jint n, jobject src, jobject dst) {
     tsx_batch_params p;
-    int rc = fill_params(env, &p, flags, key, aad, profile);
+    int rc = fill_params(env, &p, flags, key, aad, profile, level);
     if (rc == TSX_OK) {
         tsx_chunk_desc* d = (tsx_chunk_desc*)(*env)->GetDirectBufferAddress(env, descs);
         const void* s = (*env)->GetDirectBufferAddress(env, src);
@@ -97,18 +97,31 @@ static jint run(JNIEnv* env, int detransform, int mem_kind, jint flags, jbyteArr
 JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(
     JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jobject descs, jint n, jobject src, jobject dst) {
     (void)cls;
-    return run(env, 0, TSX_MEM_HOST, flags, key, aad, profile, descs, n, src, dst);
+    return run(env, 0, TSX_MEM_HOST, flags, key, aad, profile, 0, descs, n, src, dst);
+}
+
+/* ... at a Zstandard level: compression.zstd.level (1 - 3; 0 = the library default, 3); the library refuses any other */
+JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchLevel(
+    JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jint level, jobject descs, jint n, jobject src, jobject dst) {
+    (void)cls;
+    return run(env, 0, TSX_MEM_HOST, flags, key, aad, profile, level, descs, n, src, dst);
 }
 
 /* TSX_MEM_HOST_PACKED: dst is the upload's own buffer (a multipart part, a mapped file); chunk i lands at descs[i].dst_off */
 JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPacked(
     JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jobject descs, jint n, jobject src, jobject dst) {
     (void)cls;
-    return run(env, 0, TSX_MEM_HOST_PACKED, flags, key, aad, profile, descs, n, src, dst);
+    return run(env, 0, TSX_MEM_HOST_PACKED, flags, key, aad, profile, 0, descs, n, src, dst);
+}
+
+JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(
+    JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jint level, jobject descs, jint n, jobject src, jobject dst) {
+    (void)cls;
+    return run(env, 0, TSX_MEM_HOST_PACKED, flags, key, aad, profile, level, descs, n, src, dst);
 }
 
 JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_detransformBatch(
     JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jobject descs, jint n, jobject src, jobject dst) {
     (void)cls;
-    return run(env, 1, TSX_MEM_HOST, flags, key, aad, 1, descs, n, src, dst);
+    return run(env, 1, TSX_MEM_HOST, flags, key, aad, 1, 0, descs, n, src, dst);
 }

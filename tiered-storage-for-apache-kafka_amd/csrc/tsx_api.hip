@@ -691,7 +691,7 @@ extern "C" int tsx_init_ex(int device_count, const int* device_ids, const tsx_co
     g_devs.swap(devs);
     char* vb = g_version_buf[g_version_gen++ & 1];
     snprintf(vb, sizeof g_version_buf[0],
-             "tsxform 0.5 (gfx950 HIP; CRC32C, AES-256-GCM, Zstd level-3 frames; zstd parity target libzstd 1.5.7 / 1.5.6 profile; %d device(s): %s; "
+             "tsxform 0.5 (gfx950 HIP; CRC32C, AES-256-GCM, Zstd frames of levels 1-3; zstd parity target libzstd 1.5.7 / 1.5.6 profile; %d device(s): %s; "
              "compressor service: %u waves, %u of %u CUs reserved for fetches)",
              (int)g_devs.size(), g_devs[0].name, g_devs[0].svc->grid, g_devs[0].svc->cus_reserved, g_devs[0].svc->cus);
     g_version.store(vb, std::memory_order_release);
@@ -1178,7 +1178,7 @@ static int svc_submit(tsx_device* dev, const tsx_zseg& proto, const uint32_t* h_
     const uint16_t slot = s.free_slots.back(); s.free_slots.pop_back();
     const uint16_t gen = ++s.slot_gen[slot];
     tsx_zseg e = proto;
-    e.gen = gen; e.pad = 0;
+    e.gen = gen;
     s.h->member[slot] = e;
     const uint32_t first = s.published;
     for (uint32_t i = 0; i < n; i++) { tsx_svc_ticket& t = s.h->ticket[(first + i) & (TSX_SVC_TICKETS - 1)]; t.member_gen = (uint32_t)gen << 16 | slot; t.chunk = i; }
@@ -1426,7 +1426,7 @@ static int run_compress(tsx_run& r) {
             if (hipStreamSynchronize(c->st) != hipSuccess) return abandon_all(TSX_E_DEVICE);
         }
         tsx_zseg m; memset(&m, 0, sizeof m);
-        m.n = sb.n; m.profile = r.params->zstd_profile;
+        m.n = sb.n; m.profile = r.params->zstd_profile; m.level = (r.params->zstd_level == 1 || r.params->zstd_level == 2) ? (uint32_t)r.params->zstd_level : 3u;
         m.src_base = r.d_src; m.descs = (self_status ? c->hd_descs : c->d_descs) + sb.lo; m.mid = c->d_mid + (size_t)sb.lo * c->mid_stride; m.mid_stride = c->mid_stride;
         m.zlen = c->d_zlen + sb.lo; m.status = c->d_status + sb.lo; m.work = (uint8_t*)c->d_zwork + (size_t)sb.lo * tsx_zstd_workspace_bytes(1, 0);
         if (self_status) {
@@ -1793,7 +1793,7 @@ static int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc*
     if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC)) return TSX_E_INVAL;
     if (mode != 2) {
         if (params->aad_len > 64) return TSX_E_INVAL;
-        if ((flags & TSX_COMPRESS) && !(params->zstd_level == 0 || params->zstd_level == 3)) return TSX_E_UNSUPPORTED;
+        if ((flags & TSX_COMPRESS) && !(params->zstd_level >= 0 && params->zstd_level <= 3)) return TSX_E_UNSUPPORTED;   // 0 = 3 (the library default), 1, 2, 3
         if ((flags & TSX_COMPRESS) && params->zstd_profile > TSX_ZSTD_PROFILE_1_5_7) return TSX_E_UNSUPPORTED;
     }
     if (n == 0) return TSX_OK;

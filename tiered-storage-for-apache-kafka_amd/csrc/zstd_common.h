@@ -53,3 +53,34 @@ __host__ __device__ static inline zs_cparams zs_level3_cparams(uint32_t srcSize)
     if (c.windowLog < 10) c.windowLog = 10;
     return c;
 }
+
+// Levels 1 - 3 as ZSTD_getCParams(level, srcSize, 0) of libzstd 1.5.7 returns them: the row of ZSTD_defaultCParameters for the
+// source size, then ZSTD_adjustCParams_internal.  srcSize 0 = unknown (no adjustment, the > 256 KiB row), as in the library.
+// strategy: 1 = fast, 2 = dfast.  Level 2 is dfast for sources in (128 KiB, 256 KiB].  (zs_level3_cparams stays what the level-3
+// compressor has always used; it agrees with this one for every known size.)
+#define ZS_STRAT_FAST 1u
+#define ZS_STRAT_DFAST 2u
+struct zs_level_params { uint32_t windowLog, chainLog, hashLog, searchLog, minMatch, targetLength, strategy; };
+__host__ __device__ static inline zs_level_params zs_level_cparams(int level, uint64_t srcSize) {
+    //                                      wlog clog hlog slog mml tlen strategy           (levels 1, 2, 3)
+    static const uint8_t kRows[4][3][7] = {{{19, 13, 14, 1, 7, 0, 1}, {20, 15, 16, 1, 6, 0, 1}, {21, 16, 17, 1, 5, 0, 2}},   // > 256 KiB
+                                           {{18, 13, 14, 1, 6, 0, 1}, {18, 14, 14, 1, 5, 0, 2}, {18, 16, 16, 1, 4, 0, 2}},   // <= 256 KiB
+                                           {{17, 12, 13, 1, 6, 0, 1}, {17, 13, 15, 1, 5, 0, 1}, {17, 15, 16, 2, 5, 0, 2}},   // <= 128 KiB
+                                           {{14, 14, 15, 1, 5, 0, 1}, {14, 14, 15, 1, 4, 0, 1}, {14, 14, 15, 2, 4, 0, 2}}};  // <= 16 KiB
+    const uint32_t li = level <= 1 ? 0u : level == 2 ? 1u : 2u;
+    const uint32_t table = srcSize == 0 ? 0u : (srcSize <= (256u << 10)) + (srcSize <= (128u << 10)) + (srcSize <= (16u << 10));
+    const uint8_t* r = kRows[table][li];
+    zs_level_params c;
+    c.windowLog = r[0]; c.chainLog = r[1]; c.hashLog = r[2]; c.searchLog = r[3]; c.minMatch = r[4]; c.targetLength = r[5]; c.strategy = r[6];
+    if (srcSize != 0 && srcSize <= (1ull << 30)) {
+        uint32_t srcLog = 6;
+        if (srcSize >= 64) { uint64_t v = srcSize - 1; srcLog = 0; while (v) { srcLog++; v >>= 1; } }
+        if (c.windowLog > srcLog) c.windowLog = srcLog;
+    }
+    if (srcSize != 0) {
+        if (c.hashLog > c.windowLog + 1) c.hashLog = c.windowLog + 1;
+        if (c.chainLog > c.windowLog) c.chainLog = c.windowLog;            // (cycleLog = chainLog below btlazy2)
+    }
+    if (c.windowLog < 10) c.windowLog = 10;
+    return c;
+}

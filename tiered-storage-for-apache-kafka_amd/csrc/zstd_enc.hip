@@ -1,4 +1,6 @@
-// Zstandard level-3 frame compressor — gfx950, one 64-lane wavefront per chunk, up to 24 chunks resident per CU.
+// Zstandard frame compressor (levels 1 - 3) — gfx950, one 64-lane wavefront per chunk, up to 24 chunks resident per CU.
+// Levels 1 and 2 take the fast parse (fast_block) - but level 2 for sources in (128 KiB, 256 KiB], which libzstd makes dfast; the rest
+// of this header describes level 3's double-fast parse.
 //
 // Replaces zstd-jni's  new ZstdCompressCtx(); setPledgedSrcSize(n); setContentSize(true); compress(chunk)
 //   core/src/main/java/io/aiven/kafka/tieredstorage/transform/CompressionChunkEnumeration.java:50-63
@@ -155,13 +157,14 @@ __device__ static inline uint32_t tag8(uint64_t u, uint32_t hBitsL, uint32_t tag
 __device__ static inline uint32_t tag4(uint32_t u, uint32_t tagBits) { return tagBits ? (u * 0x85EBCA6Bu) >> (32 - tagBits) : 0u; }
 
 // ---- LDS state of one chunk (one wave per workgroup) --------------------------------------------------------
+#define ZS_SCAL_MULT 15
 struct HufTable { uint16_t val[256]; uint8_t nb[256]; uint32_t tableLog, maxSym; };
 struct FseTable { uint16_t state[512]; uint32_t dnb[56]; int32_t dfs[56]; uint32_t tableLog; };
 struct NodeElt { uint32_t count; uint16_t parent; uint8_t byte; uint8_t nbBits; };
 
 struct EncLds {
     int hufRepeat[2];           // 0 none, 1 check
-    uint32_t scal[16];          // lane-0 -> wave broadcast slots
+    uint32_t scal[16];          // lane-0 -> wave broadcast slots; [ZS_SCAL_MULT]: 10 - strategy of the chunk (ZSTD_selectEncodingType)
     union alignas(16) {
         struct {                // entropy stage of a block
             // The two Huffman tables of the literal stage ([cur] = table of the previous compressed-literals block, [cur ^ 1] =
@@ -650,6 +653,150 @@ __device__ ZS_NOINLINE static void match_block(const uint8_t* __restrict__ src, 
     ms.litSize = litSize + ms.lastLL;
 #undef STORE_SEQ
     PT(4);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// fast match finder for one block (strategy fast, levels 1 and 2: ZSTD_compressBlock_fast_noDict_generic of libzstd 1.5.x).
+// The serial code visits positions in pairs (a, a + 1); the next pair starts `step` further on (2 after every match, + 1 each 128 bytes
+// without one), and each pair is preceded by a repcode check at the first position of the pair after it.  For every position it reads
+// the table entry, writes its own index there and compares 4 bytes with the candidate, so a table ends up holding the last position of
+// each bucket.  Here one wave step takes up to 31 pairs (two lanes each) at once: every lane hashes its position, a lane whose bucket an
+// earlier lane of the step shares takes that lane's position as its candidate instead of the table's (what the serial read would see),
+// and of the events in serial order (repcode at the next pair, match at a, match at a + 1) the first one wins.  The writes the serial
+// code made up to that event are committed, one lane per bucket (the last one).  Table values are libzstd's indices = position + 2.
+// ---------------------------------------------------------------------------------------------------
+__device__ static inline uint32_t hashF(uint64_t u, uint32_t h, uint32_t mls) {
+    if (mls == 5) return (uint32_t)(((u << 24) * 889523592379ULL) >> (64 - h));
+    if (mls == 6) return (uint32_t)(((u << 16) * 227718039650203ULL) >> (64 - h));
+    if (mls == 7) return (uint32_t)(((u << 8) * 58295818150454627ULL) >> (64 - h));
+    return ((uint32_t)u * 2654435761U) >> (32 - h);                       // mls == 4
+}
+#define ZS_FAST_PAIRS0 4u     /* pairs of the first wave step after a match (most matches follow within a few positions) */
+#define ZS_FAST_PAIRS 31u     /* ... of every later step (lane 2 x 31 = 62 holds the first position of the pair after the last) */
+__device__ ZS_NOINLINE static void fast_block(const uint8_t* __restrict__ src, const uint32_t blockStart, const uint32_t blockSize_,
+                                              uint32_t* __restrict__ table, const zs_cparams cp, const uint32_t dictLimitIn, uint32_t* rep,
+                                              zs_seq* __restrict__ seqs, MfState& ms, uint32_t* ring, const uint32_t lane) {
+    const gbytes_t gsrc = (gbytes_t)uni_ptr(src);
+    const gwords_t gT = (gwords_t)uni_ptr(table);
+    ZS_GLOBAL zs_seq* const gseqs = (ZS_GLOBAL zs_seq*)uni_ptr(seqs);
+    const uint32_t iend = UNI(blockStart + blockSize_), dictLimit = UNI(dictLimitIn), maxDist = 1u << UNI(cp.windowLog);
+    const uint32_t plowIdx = (iend + 2 - dictLimit > maxDist) ? iend + 2 - maxDist : dictLimit;    // prefixStartIndex
+    const uint32_t lowPos = plowIdx - 2;
+    const uint32_t hlog = UNI(cp.hashLog), mls = UNI(cp.minMatch);
+    uint32_t nbSeq = 0, litSize = 0;
+    uint32_t ip = UNI(blockStart), anchor = ip;
+    uint32_t off1 = UNI(rep[0]), off2 = UNI(rep[1]), sav1 = 0, sav2 = 0;
+    if (ip + 2 == plowIdx) ip++;
+    {   const uint32_t cur = ip + 2, windowLow = (cur - dictLimit > maxDist) ? cur - maxDist : dictLimit, maxRep = cur - windowLow;
+        if (off2 > maxRep) { sav2 = off2; off2 = 0; }
+        if (off1 > maxRep) { sav1 = off1; off1 = 0; }
+    }
+    Win w; w.lo = w.hi = 0;                                           // no LDS window: the count helpers read global memory
+#define STORE_SEQ(ll_, lp_, ob_, ml_) do { if (lane == 0) zs_put_seq(&gseqs[nbSeq], (ob_), (ll_), (ml_) - 3, (lp_)); \
+                                           litSize += (ll_); nbSeq++; } while (0)
+    if (blockSize_ >= 8) {
+        const uint32_t ilimit = iend - 8;
+        const uint32_t jl = lane >> 1, role = lane & 1u;
+        for (;;) {                                                    // _start: a match ended at ip (or the block begins)
+            uint32_t a = ip, an = ip + 2, s = 2, ns = ip + 128;       // pair k: a_k, a_(k+1), step of iteration k, nextStep
+            if (an + 1 >= ilimit) break;
+            uint32_t np = ZS_FAST_PAIRS0;
+            uint32_t evType = 0, evLane = 0;
+            for (;;) {                                                // one wave step: pairs 0 .. np - 1 from (a, an, s, ns)
+                uint32_t la = 0, lan = 0, ls = 0, lns = 0;            // this lane's pair: a_j, a_(j+1), step and nextStep of iteration j
+                uint32_t ta = a, tan = an, tsv = s, tns = ns;
+                for (uint32_t j = 0; j <= np; j++) {
+                    if (j == jl) { la = ta; lan = tan; ls = tsv; lns = tns; }
+                    const uint32_t nn = tan + tsv;                    // a_(j+2)
+                    ta = tan; tan = nn;
+                    if (nn >= tns) { tsv++; tns += 128; }
+                }
+                const uint32_t pos = la + role;
+                const bool inPair = jl < np && lan + 1 < ilimit;      // iteration j runs (ip3 < ilimit)
+                const bool hashed = jl <= np && pos <= ilimit;       // (+ the first position after the last pair: the write a match at a + 1 may add)
+                const uint64_t d8 = gld64(gsrc + (hashed ? pos : ip));
+                const uint32_t h = hashed ? hashF(d8, hlog, mls) : 0xFFFFFFFFu;
+                // the serial read of this position comes after the writes of every earlier lane's position
+                uint32_t cand = 0, later = 64;
+                bool local = false;
+                const uint32_t last = 2 * np;
+                for (uint32_t i = 0; i <= last; i++) {
+                    const uint32_t hi = __builtin_amdgcn_readlane(h, i), pi = __builtin_amdgcn_readlane(pos, i);
+                    if (hi == h) {
+                        if (i < lane) { cand = pi + 2; local = true; }
+                        else if (i > lane && later == 64) later = i;
+                    }
+                }
+                if (inPair && !local) cand = gT[h];
+                bool mOK = false, rOK = false;
+                if (inPair && cand >= plowIdx) mOK = gld32(gsrc + (cand - 2)) == (uint32_t)d8;
+                if (inPair && role == 0 && off1 > 0 && lan >= off1) rOK = gld32(gsrc + lan) == gld32(gsrc + (lan - off1));
+                const unsigned long long evm = __ballot(mOK || rOK);
+                const unsigned long long validm = __ballot(inPair);
+                uint32_t lastLane;                                    // writes of lanes 0 .. lastLane are committed
+                if (evm) {
+                    evLane = (uint32_t)__ffsll((long long)evm) - 1;
+                    const uint32_t rf = __builtin_amdgcn_readlane((uint32_t)rOK, evLane);
+                    evType = (evLane & 1u) ? 3u : rf ? 1u : 2u;       // 1 repcode at the next pair, 2 match at a, 3 match at a + 1
+                    lastLane = (evLane | 1u);
+                    if (evType == 3 && __builtin_amdgcn_readlane(ls, evLane) <= 4) lastLane++;
+                } else {
+                    lastLane = validm ? 63u - (uint32_t)__clzll((long long)validm) : 0u;
+                }
+                if (validm && lane <= lastLane && later > lastLane) gT[h] = pos + 2;
+                if (evm) {
+                    // ---- the event: sequence, table fill, immediate repcodes ----
+                    const uint32_t pf = __builtin_amdgcn_readlane(pos, evLane);
+                    const uint32_t cur0 = pf;                         // (the serial code's current0: the pair's a for a repcode)
+                    uint32_t st, mpos, mlen, offBase;
+                    if (evType == 1) {
+                        st = __builtin_amdgcn_readlane(lan, evLane); mpos = st - off1;
+                        const uint32_t b1 = src[st - 1] == src[mpos - 1];
+                        st -= b1; mpos -= b1; mlen = 4 + b1; offBase = 1;
+                    } else {
+                        mpos = __builtin_amdgcn_readlane(cand, evLane) - 2;
+                        off2 = off1; off1 = pf - mpos; offBase = off1 + 3;
+                        const uint32_t back = UNI(count_more_back(src, ring, w, pf, mpos, anchor, lowPos, lane));
+                        st = pf - back; mpos -= back; mlen = 4 + back;
+                    }
+                    mlen += UNI(count_more(src, ring, w, st + mlen, mpos + mlen, iend, lane));
+                    STORE_SEQ(st - anchor, anchor, offBase, mlen);
+                    ip = UNI(st + mlen); anchor = ip;
+                    off1 = UNI(off1); off2 = UNI(off2);
+                    if (ip <= ilimit) {
+                        WAVE_MEM_SYNC();                              // (emulator) after the step's own writes
+                        if (lane == 0) {
+                            gT[hashF(gld64(gsrc + cur0 + 2), hlog, mls)] = cur0 + 4;
+                            gT[hashF(gld64(gsrc + ip - 2), hlog, mls)] = ip;
+                        }
+                        while (off2 > 0 && ip <= ilimit && gld32(gsrc + ip) == gld32(gsrc + (ip - off2))) {
+                            const uint32_t rl = 4 + UNI(count_more(src, ring, w, ip + 4, ip + 4 - off2, iend, lane));
+                            const uint32_t t = off2; off2 = off1; off1 = t;
+                            WAVE_MEM_SYNC();
+                            if (lane == 0) gT[hashF(gld64(gsrc + ip), hlog, mls)] = ip + 2;
+                            STORE_SEQ(0, ip, 1, rl);
+                            ip += rl; anchor = ip;
+                        }
+                    }
+                    WAVE_MEM_SYNC();
+                    break;
+                }
+                if (!validm || __builtin_amdgcn_readlane((uint32_t)inPair, 2 * np - 2) == 0) { evType = 4; break; }    // the block's tail
+                // no event: go on from pair np
+                a = __builtin_amdgcn_readlane(la, 2 * np); an = __builtin_amdgcn_readlane(lan, 2 * np);
+                s = __builtin_amdgcn_readlane(ls, 2 * np); ns = __builtin_amdgcn_readlane(lns, 2 * np);
+                WAVE_MEM_SYNC();
+                np = ZS_FAST_PAIRS;
+            }
+            if (evType == 4) break;
+        }
+    }
+    sav2 = (sav1 != 0 && off1 != 0) ? sav1 : sav2;
+    rep[0] = off1 ? off1 : sav1;
+    rep[1] = off2 ? off2 : sav2;
+    ms.nbSeq = nbSeq; ms.lastLL = iend - anchor; ms.anchor = anchor;
+    ms.litSize = litSize + ms.lastLL;
+#undef STORE_SEQ
 }
 
 // Per-lane copy of a short run with up to 32 bytes of loads in flight before the first store (a byte loop would pay one
@@ -1393,10 +1540,10 @@ __device__ ZS_NOINLINE static uint32_t compress_literals(uint8_t* dst, const uin
 // sequences section (ZSTD_buildSequencesStatistics + ZSTD_encodeSequences).  Returns bytes written at op,
 // 0xFFFFFFFF if the block must be emitted raw.
 // ---------------------------------------------------------------------------------------------------
-__device__ static int select_encoding(uint32_t mostFrequent, uint32_t nbSeq, uint32_t defaultNormLog, bool defaultAllowed) {
+__device__ static int select_encoding(uint32_t mostFrequent, uint32_t nbSeq, uint32_t defaultNormLog, bool defaultAllowed, uint32_t mult) {
     if (mostFrequent == nbSeq) return (defaultAllowed && nbSeq <= 2) ? 0 : 1;           // set_basic : set_rle
     if (defaultAllowed) {
-        const uint32_t dynMin = ((1u << defaultNormLog) * 8u) >> 3;                      // mult = 10 - strategy(2)
+        const uint32_t dynMin = ((1u << defaultNormLog) * mult) >> 3;                    // mult = 10 - strategy (9 fast, 8 dfast)
         if (nbSeq < dynMin || mostFrequent < (nbSeq >> (defaultNormLog - 1))) return 0;   // set_basic
     }
     return 2;                                                                            // set_compressed
@@ -1410,7 +1557,7 @@ __device__ ZS_NOINLINE static uint32_t build_seq_table(uint8_t* op, FseTable& ct
     uint32_t mostFrequent = 0;
     for (uint32_t s = 0; s <= max; s++) if (cnt[s] > mostFrequent) mostFrequent = cnt[s];
     const bool defaultAllowed = isOffsets ? (max <= ZS_DefaultMaxOff) : true;
-    const int t = select_encoding(mostFrequent, nbSeq, defaultNormLog, defaultAllowed);
+    const int t = select_encoding(mostFrequent, nbSeq, defaultNormLog, defaultAllowed, L.scal[ZS_SCAL_MULT]);
     *type = (uint32_t)t;
     if (t == 1) {                                                          // rle
         ct.tableLog = 0; ct.state[0] = 0; ct.state[1] = 0; ct.dnb[max] = 0; ct.dfs[max] = 0;
@@ -1609,6 +1756,41 @@ __device__ ZS_NOINLINE static uint32_t split_block_1_5_7(const uint8_t* __restri
     return ZS_BLOCK_MAX;
 }
 
+// libzstd 1.5.7 pre-block splitter of strategy fast (ZSTD_splitBlock_fromBorders): byte histograms of the first and the last 512 bytes
+// of the 128 KiB block; when they differ, the histogram of the middle 512 bytes decides between 32, 64 and 96 KiB.
+__device__ ZS_NOINLINE static uint32_t split_block_fast_1_5_7(const uint8_t* __restrict__ p, EncLds& L, uint32_t lane) {
+    uint32_t* h0 = L.hist; uint32_t* h1 = L.hist2;
+    for (uint32_t i = lane; i < 256; i += LANES) { h0[i] = 0; h1[i] = 0; }
+    __syncthreads();
+    for (uint32_t n = lane; n < 512; n += LANES) { atomicAdd(&h0[p[n]], 1u); atomicAdd(&h1[p[ZS_BLOCK_MAX - 512 + n]], 1u); }
+    __syncthreads();
+    uint32_t past[4], fresh[4];
+    uint64_t dev = 0;
+    for (uint32_t k = 0; k < 4; k++) {
+        past[k] = h0[lane + k * LANES]; fresh[k] = h1[lane + k * LANES];
+        const int64_t d = (int64_t)past[k] * 512 - (int64_t)fresh[k] * 512;
+        dev += (uint64_t)(d < 0 ? -d : d);
+    }
+    for (int o = 32; o; o >>= 1) dev += __shfl_xor(dev, o);
+    if (dev < (uint64_t)512 * 512 * 14 / 16) return ZS_BLOCK_MAX;     // compareFingerprints(penalty 0): not "too different"
+    __syncthreads();
+    for (uint32_t i = lane; i < 256; i += LANES) h0[i] = 0;
+    __syncthreads();
+    for (uint32_t n = lane; n < 512; n += LANES) atomicAdd(&h0[p[ZS_BLOCK_MAX / 2 - 256 + n]], 1u);
+    __syncthreads();
+    uint64_t dB = 0, dE = 0;
+    for (uint32_t k = 0; k < 4; k++) {
+        const int64_t m = (int64_t)h0[lane + k * LANES] * 512;
+        const int64_t x = (int64_t)past[k] * 512 - m, y = (int64_t)fresh[k] * 512 - m;
+        dB += (uint64_t)(x < 0 ? -x : x); dE += (uint64_t)(y < 0 ? -y : y);
+    }
+    for (int o = 32; o; o >>= 1) { dB += __shfl_xor(dB, o); dE += __shfl_xor(dE, o); }
+    __syncthreads();
+    const int64_t diff = (int64_t)dB - (int64_t)dE;
+    if ((diff < 0 ? -diff : diff) < 512 * 512 / 3) return 64u << 10;
+    return dB > dE ? 32u << 10 : 96u << 10;
+}
+
 __device__ static bool wave_is_rle(const uint8_t* __restrict__ p, uint32_t n, uint32_t lane) {
     const uint8_t b0 = p[0];
     bool bad = false;
@@ -1690,7 +1872,7 @@ __device__ static inline uint32_t svc_cu_key();                        // (which
 // a fetch that does not start, once in a few hundred fetches" of round 5 (profiles/r06_stuck_fetch_trace.txt).
 __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint8_t* __restrict__ src_base, tsx_chunk_desc* __restrict__ descs,
                                                            uint8_t* __restrict__ mid, uint64_t mid_stride, uint32_t* __restrict__ zlen,
-                                                           int32_t* __restrict__ status, uint8_t* __restrict__ work, uint32_t profile, uint32_t sched,
+                                                           int32_t* __restrict__ status, uint8_t* __restrict__ work, uint32_t profile, uint32_t level, uint32_t sched,
                                                            const tsx_chain_fuse fuse, const uint32_t chunk, const uint32_t* yield, const uint32_t* reserved
 #ifdef TSX_PROF
                                                            , unsigned long long* __restrict__ prof_out
@@ -1720,12 +1902,20 @@ __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint
     if (fuse.self_status) { if (lane == 0) status[chunk] = TSX_OK; }    // (finish_frame publishes the chunk's final status in its descriptor)
     else if (status[chunk] != TSX_OK) { if (lane == 0) { zlen[chunk] = 0; if (fuse.key) descs[chunk].dst_len = 0; } return false; }
 
-    const zs_cparams cp = zs_level3_cparams(srcSize);
-    {   // fresh tables (ZSTD_reset_matchState): zero hashLong[1 << hashLog] and hashSmall[1 << chainLog]
+    // level 1 or 2 (tsx_zseg.level); anything else is level 3.  Level 1 and level 2 outside (128 KiB, 256 KiB] are strategy fast: one table
+    // (hashLong's place), the fast parse and the fast pre-splitter; level 2 inside that band is dfast like level 3, with its own parameters.
+    zs_cparams cp = zs_level3_cparams(srcSize);
+    bool fast = false;
+    if (level == 1 || level == 2) {
+        const zs_level_params q = zs_level_cparams((int)level, srcSize ? srcSize : 1);
+        cp.windowLog = q.windowLog; cp.chainLog = q.chainLog; cp.hashLog = q.hashLog; cp.minMatch = q.minMatch;
+        fast = q.strategy == ZS_STRAT_FAST;
+    }
+    {   // fresh tables (ZSTD_reset_matchState): zero hashLong[1 << hashLog] and (dfast) hashSmall[1 << chainLog]
         uint4 z; z.x = z.y = z.z = z.w = 0;
         uint4* a = (uint4*)hashLong; uint4* b = (uint4*)hashSmall;
         for (uint32_t i = lane; i < (1u << cp.hashLog) / 4; i += LANES) a[i] = z;
-        for (uint32_t i = lane; i < (1u << cp.chainLog) / 4; i += LANES) b[i] = z;
+        if (!fast) for (uint32_t i = lane; i < (1u << cp.chainLog) / 4; i += LANES) b[i] = z;
     }
     // ---- frame header (ZSTD_writeFrameHeader: content size known, no checksum, no dictID) ----
     uint32_t hdr = 0;
@@ -1749,6 +1939,7 @@ __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint
         return false;
     }
     uint32_t* const hufSave = (uint32_t*)(ws + ZS_WS_HUFSAVE);
+    if (lane == 0) L.scal[ZS_SCAL_MULT] = fast ? 10u - ZS_STRAT_FAST : 10u - ZS_STRAT_DFAST;
     static_assert(sizeof(L.huf) % 4 == 0 && sizeof(L.huf) <= 2048, "Huffman tables fit their place in the workspace");
     if (lane == 0) { L.hufRepeat[0] = 0; L.hufRepeat[1] = 0; L.huf[0].maxSym = 0; L.huf[1].maxSym = 0; }
     __syncthreads();
@@ -1774,7 +1965,7 @@ __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint
         // ---- block size (ZSTD_optimalBlockSize) ----
         uint32_t blockSize = remaining < blockSizeMax ? remaining : blockSizeMax;
         if (profile == TSX_ZSTD_PROFILE_1_5_7 && remaining >= ZS_BLOCK_MAX && blockSizeMax >= ZS_BLOCK_MAX && savings >= 3)
-            blockSize = UNI(split_block_1_5_7(src + ipos, L, lane));
+            blockSize = fast ? UNI(split_block_fast_1_5_7(src + ipos, L, lane)) : UNI(split_block_1_5_7(src + ipos, L, lane));
         PT(1);
         const uint32_t lastBlock = blockSize == remaining;
         {   // ZSTD_window_enforceMaxDist(&ms->window, ip, maxDist, ...): libzstd >= 1.5.0 slides the window to the block's start
@@ -1785,7 +1976,8 @@ __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint
         if (blockSize >= 7) {
             uint32_t rep[3] = {repc[0], repc[1], repc[2]};
             MfState ms;
-            match_block(src, srcSize, ipos, blockSize, hashLong, hashSmall, cp, dictLimit, rep, seqs, ms, L.p.ring, L.p.scr, lane, sched);
+            if (fast) fast_block(src, ipos, blockSize, hashLong, cp, dictLimit, rep, seqs, ms, L.p.ring, lane);
+            else match_block(src, srcSize, ipos, blockSize, hashLong, hashSmall, cp, dictLimit, rep, seqs, ms, L.p.ring, L.p.scr, lane, sched);
             __threadfence_block();
             __syncthreads();
             gather_literals(lit, src, seqs, ms.nbSeq, ms.anchor, ms.lastLL, lane);
@@ -2119,7 +2311,7 @@ __global__ __launch_bounds__(LANES, ZS_WAVES_PER_SIMD) void zstd_service_kernel(
         uint64_t w = 0;
         if (lane < 16 && slot < TSX_SVC_MEMBERS) w = SVC_LD_SYS(reinterpret_cast<const uint64_t*>(&H->member[slot]) + lane);
         const uint64_t w0 = svc_word(w, 0), w1 = svc_word(w, 1);
-        const uint32_t n = (uint32_t)w0, profile = (uint32_t)(w0 >> 32), gen = (uint32_t)w1;
+        const uint32_t n = (uint32_t)w0, profile = (uint32_t)(w0 >> 32), gen = (uint32_t)w1, level = (uint32_t)(w1 >> 32);
         if (slot >= TSX_SVC_MEMBERS || (gen & 0xFFFFu) != (mg >> 16) || chunk >= n) {          // an abandoned member's ticket
             if (lane == 0) { atomicAdd(&D->stat_skipped, 1u); atomicAdd(&D->fin, 1u); atomicSub(&D->cu_busy[key_busy], 1u); atomicSub(&D->busy, 1u); }
             continue;
@@ -2130,7 +2322,7 @@ __global__ __launch_bounds__(LANES, ZS_WAVES_PER_SIMD) void zstd_service_kernel(
         { const uint64_t f = svc_word(w, 13); fuse.self_status = (uint32_t)f; fuse.key_on_host = (uint32_t)(f >> 32); }
         uint32_t* const done = (uint32_t*)svc_word(w, 14); uint32_t* const flag = (uint32_t*)svc_word(w, 15);
         const bool handed_back = zstd_compress_chunk(L, (const uint8_t*)svc_word(w, 2), (tsx_chunk_desc*)svc_word(w, 3), (uint8_t*)svc_word(w, 4), svc_word(w, 5),
-                            (uint32_t*)svc_word(w, 6), (int32_t*)svc_word(w, 7), (uint8_t*)svc_word(w, 8), profile, a.sched, fuse, chunk, off_limits ? &H->yield : (a.guests & 2u) ? yield : nullptr, off_limits ZS_PROF_ARG);
+                            (uint32_t*)svc_word(w, 6), (int32_t*)svc_word(w, 7), (uint8_t*)svc_word(w, 8), profile, level, a.sched, fuse, chunk, off_limits ? &H->yield : (a.guests & 2u) ? yield : nullptr, off_limits ZS_PROF_ARG);
 #ifdef TSX_PROF
         if (lane == 0 && prof_out && !handed_back) { prof_out[(size_t)chunk * 24 + 21] = t_start; prof_out[(size_t)chunk * 24 + 22] = g_prof_take; prof_out[(size_t)chunk * 24 + 19] |= (unsigned long long)key_busy << 20; }   // [21], [22]: when this wave began, when it had the ticket
 #endif

@@ -293,11 +293,11 @@ std::string Backend::version() const { return f_->version(); }
 
 static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-static tsx_batch_params makeParams(uint32_t flags, const Bytes* key, const Bytes* aad, uint32_t profile) {
+static tsx_batch_params makeParams(uint32_t flags, const Bytes* key, const Bytes* aad, uint32_t profile, int level = 0) {
     tsx_batch_params p;
     memset(&p, 0, sizeof p);
     p.flags = flags;
-    p.zstd_level = 0;
+    p.zstd_level = level;
     p.zstd_profile = profile;
     if (flags & TSX_ENCRYPT) {
         if (!key || key->size() != 32) throw std::invalid_argument("AES-256 data key must be 32 bytes");
@@ -454,10 +454,12 @@ Bytes BaseTransformChunkEnumeration::nextElement() {
 }
 
 GpuTransformChunkEnumeration::GpuTransformChunkEnumeration(std::shared_ptr<Backend> be, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
-                                                           std::optional<DataKeyAndAAD> enc, IvSupplier iv, int batchChunks, bool withCrc, uint32_t profile, bool readAhead)
+                                                           std::optional<DataKeyAndAAD> enc, IvSupplier iv, int batchChunks, bool withCrc, uint32_t profile, bool readAhead,
+                                                           int zstdLevel)
     : be_(std::move(be)), inner_(std::move(inner)), compress_(compress), enc_(std::move(enc)), iv_(std::move(iv)), batch_(batchChunks), withCrc_(withCrc),
-      profile_(profile), readAhead_(readAhead) {
+      profile_(profile), readAhead_(readAhead), level_(zstdLevel) {
     if (!inner_) throw std::invalid_argument("inner cannot be null");
+    if (level_ < 0 || level_ > 3) throw std::invalid_argument("zstd level must be 1, 2 or 3 (0 = library default), " + std::to_string(level_) + " given");
     if (batch_ < 1) throw std::invalid_argument("batchChunks must be positive");
     if (enc_ && enc_->dataKey.size() != 32) throw std::invalid_argument("AES-256 data key must be 32 bytes");
     // CompressionChunkEnumeration.java:39-42 (null) then EncryptionChunkEnumeration.java:41-47 (inner + ivSize + getOutputSize)
@@ -487,7 +489,7 @@ GpuTransformChunkEnumeration::Batch GpuTransformChunkEnumeration::transformNextB
     }
     Bytes src(so + 16), dst(dofs + 16);
     for (size_t i = 0; i < in.size(); i++) memcpy(src.data() + d[i].src_off, in[i].data(), in[i].size());
-    const tsx_batch_params p = makeParams(flags, enc_ ? &enc_->dataKey : nullptr, enc_ ? &enc_->aad : nullptr, profile_);
+    const tsx_batch_params p = makeParams(flags, enc_ ? &enc_->dataKey : nullptr, enc_ ? &enc_->aad : nullptr, profile_, level_);
     be_->transformBatch(p, d, src.data(), src.size(), dst.data(), dst.size());
     for (size_t i = 0; i < in.size(); i++) {
         if (d[i].status != TSX_OK) throw std::runtime_error(be_->strerror(d[i].status));        // the reference wraps crypto failures in RuntimeException
@@ -531,7 +533,7 @@ GpuTransformChunkEnumeration::PackedBatch GpuTransformChunkEnumeration::transfor
     }
     Bytes src(so + 16);
     for (size_t i = 0; i < in.size(); i++) if (!in[i].empty()) memcpy(src.data() + d[i].src_off, in[i].data(), in[i].size());
-    const tsx_batch_params p = makeParams(flags, enc_ ? &enc_->dataKey : nullptr, enc_ ? &enc_->aad : nullptr, profile_);
+    const tsx_batch_params p = makeParams(flags, enc_ ? &enc_->dataKey : nullptr, enc_ ? &enc_->aad : nullptr, profile_, level_);
     out.object.resize(bound);                                          // room for the worst case, trimmed to what was produced
     be_->transformBatchPacked(p, d, src.data(), src.size(), out.object.data(), bound);
     size_t total = 0;

@@ -246,8 +246,12 @@ public:
     // fed by a handful of threads ("stragglers").  Off: `inner` is read exactly when the reference would read it.
     GpuTransformChunkEnumeration(std::shared_ptr<Backend> backend, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                  std::optional<DataKeyAndAAD> encryption, IvSupplier ivSupplier = secureRandomIvSupplier(),
-                                 int batchChunks = 64, bool withCrc = false, uint32_t zstdProfile = TSX_ZSTD_PROFILE_1_5_7, bool readAhead = true);
+                                 int batchChunks = 64, bool withCrc = false, uint32_t zstdProfile = TSX_ZSTD_PROFILE_1_5_7, bool readAhead = true,
+                                 int zstdLevel = 0);
     ~GpuTransformChunkEnumeration() override;
+    // Zstandard level of the frames (compression.zstd.level): 0 = the library default (3, what the reference uses), 1, 2 or 3;
+    // anything else is refused here, not at the first batch
+    int zstdLevel() const { return level_; }
     int originalChunkSize() const override { return inner_->originalChunkSize(); }
     std::optional<int> transformedChunkSize() const override { return transformedChunkSize_; }
     bool hasMoreElements() override;
@@ -276,6 +280,7 @@ private:
     bool withCrc_;
     uint32_t profile_;
     bool readAhead_;
+    int level_;
     std::optional<int> transformedChunkSize_;
     std::vector<Bytes> ready_;
     size_t next_ = 0;
@@ -323,6 +328,7 @@ public:
     size_t readSome(uint8_t* b, size_t len);               // at most what the current batch still holds; 0 at the object's end
     std::shared_ptr<ChunkIndex> chunkIndex();              // "Chunk index was not built, was finisher used?" until the object has been drained
     const std::vector<uint32_t>& crc32cOfOriginalChunks() const { return crcs_; }
+    int zstdLevel() const { return inner_->zstdLevel(); }   // the enumeration's (the finisher transforms through it)
 
 private:
     bool nextBatch();

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Zstandard levels 1, 2 and 3 side by side on one device, one process: bench.py's `value` shape (8 x 1 GiB segments of content K resident
+in HBM, 4 MiB chunks, CRC32C + Zstd + AES-256-GCM, 5 callers, device-resident batches) and its `value_B` shape (64 distinct chunks of content
+B replicated over the same batch).  The levels run in alternating order (1 2 3, then 3 2 1, ...); for every run: GiB/s of original bytes,
+transformed / original, and the compressor service's kernel time; a sample of every level's timed chunks is checked against libzstd
+(+ the oracle's GCM).  One JSON line per run, then a summary line.
+  python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8]"""
+import argparse
+import json
+import os
+import sys
+import threading
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+GiB = float(1 << 30)
+
+
+def _gen_b_chunk(a):
+    """(worker of a spawned process pool) one chunk of content B."""
+    from tsxform import synth
+    return synth.gen_chunk("B", a[0], a[1], a[2], a[3])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--callers", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=2, help="each round runs every level once; odd rounds in reverse order")
+    ap.add_argument("--contents", default="K,B")
+    ap.add_argument("--segments", type=int, default=8)
+    ap.add_argument("--check", type=int, default=16, help="timed chunks per run checked against libzstd")
+    ap.add_argument("--levels", default="1,2,3")
+    args = ap.parse_args()
+
+    import torch  # before libtsxform: one shared HIP runtime
+    import tsxform
+    from oracle import oracle as o
+    from tsxform import synth
+    nat = tsxform._native
+    N = tsxform.get()
+    dev = torch.device("cuda", 0)
+    CH, cps = synth.CHUNK, 256
+    n = args.segments * cps
+    T = args.callers
+    flags = nat.COMPRESS | nat.ENCRYPT | nat.CRC
+    levels = [int(x) for x in args.levels.split(",")]
+    slot = (N.transformed_bound(CH, flags) + 63) // 64 * 64
+    src = torch.empty(n * CH, dtype=torch.uint8, device=dev)
+    dsts = [torch.empty(n * slot, dtype=torch.uint8, device=dev) for _ in range(T)]
+    d = np.zeros(n, nat.DESC_DTYPE)
+    d["src_off"] = np.arange(n, dtype=np.uint64) * CH; d["src_len"] = CH
+    d["dst_off"] = np.arange(n, dtype=np.uint64) * slot; d["dst_cap"] = slot
+    for i in range(n):
+        d["iv"][i] = np.frombuffer(synth.iv_for(i // cps, i % cps), np.uint8)
+    ctxs = [N.ctx_create(0, n, CH) for _ in range(T)]
+    rows = []
+    for content in args.contents.split(","):
+        t_gen = time.perf_counter()
+        if content == "K":
+            for i in range(n):
+                src[i * CH:(i + 1) * CH] = synth.gen_chunk("K", 1000 + i // cps, i // cps, i % cps, CH, device=dev)
+            distinct = n
+
+            def host_chunk(i):
+                return src[i * CH:(i + 1) * CH].cpu().numpy()
+        else:
+            import multiprocessing as mp
+            from concurrent.futures import ProcessPoolExecutor
+            distinct = 64
+            with ProcessPoolExecutor(16, mp_context=mp.get_context("spawn")) as ex:
+                hb = list(ex.map(_gen_b_chunk, [(1000, 0, c, CH) for c in range(distinct)]))
+            for i in range(n):
+                src[i * CH:(i + 1) * CH] = torch.from_numpy(hb[i % distinct]).to(dev)
+
+            def host_chunk(i, hb=hb):
+                return hb[i % distinct]
+        torch.cuda.synchronize()
+        gen_s = time.perf_counter() - t_gen
+        order = []
+        for r in range(args.rounds):
+            order += levels if r % 2 == 0 else levels[::-1]
+        for level in order:
+            p = nat.Native.make_params(flags, synth.KEY, synth.AAD, zstd_level=level)
+            ds = [d.copy() for _ in range(T)]
+
+            def step(t):
+                N.transform_batch(p, ds[t], src.data_ptr(), dsts[t].data_ptr(), dsts[t].numel(), nat.MEM_DEVICE, ctx=ctxs[t])
+            for w in range(max(args.warmup, 1)):
+                for t in (range(T) if w == 0 else range(1)):
+                    step(t)
+            torch.cuda.synchronize()
+            N.service_quiesce(0)
+            s0 = N.service_stats(0)
+
+            def worker(t):
+                for _ in range(t, args.steps, T):
+                    step(t)
+            t0 = time.perf_counter()
+            th = [threading.Thread(target=worker, args=(t,)) for t in range(T)]
+            [x.start() for x in th]
+            [x.join() for x in th]
+            torch.cuda.synchronize()
+            el = time.perf_counter() - t0
+            N.service_quiesce(0)
+            s1 = N.service_stats(0)
+            ok = all(bool((x["status"] == 0).all()) for x in ds) and all(bool((x["dst_len"] == ds[0]["dst_len"]).all()) for x in ds)
+            rng = np.random.default_rng(level * 1000 + len(rows))
+            sample = sorted(set(int(i) for i in rng.integers(0, n, args.check))) if content == "K" else list(range(min(args.check, distinct)))
+            host = dsts[0]
+            for i in sample:
+                got = host[i * slot:i * slot + int(ds[0]["dst_len"][i])].cpu().numpy().tobytes()
+                raw = np.ascontiguousarray(host_chunk(i)).tobytes()
+                exp = o.gcm_encrypt_chunk(synth.KEY, ds[0]["iv"][i].tobytes(), synth.AAD, o.zstd_compress_chunk(raw, level))
+                ok = ok and got == exp
+            row = {"content": content, "level": level, "gibs": round(args.steps * n * CH / GiB / el, 3), "elapsed_s": round(el, 3),
+                   "ratio": round(float(ds[0]["dst_len"].astype(np.int64).sum() - 28 * n) / (n * CH), 4),
+                   "kernel_ms": round(s1["kernel_ms"] - s0["kernel_ms"], 1), "launches": s1["launches"] - s0["launches"],
+                   "chunks": n, "distinct_chunks": distinct, "steps": args.steps, "callers": T,
+                   "checked_chunks": len(sample), "exact_vs_libzstd": bool(ok), "generated_in_s": round(gen_s, 1)}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    summary = {}
+    for r in rows:
+        k = "%s_L%d" % (r["content"], r["level"])
+        summary.setdefault(k, []).append(r["gibs"])
+    print(json.dumps({"metric": "GiB/s of original bytes per level (runs in order)", "runs": summary,
+                      "ratio": {"%s_L%d" % (r["content"], r["level"]): r["ratio"] for r in rows},
+                      "all_exact": all(r["exact_vs_libzstd"] for r in rows), "libzstd": o.zstd_version(), "tsxform": N.version()}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
