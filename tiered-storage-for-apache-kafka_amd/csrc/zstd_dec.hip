@@ -17,6 +17,9 @@
 //           then every lane extracts its own sequence's extra bits; repeat offsets resolved in order -> arrays k & 1
 //   wave 2  execution: 64 sequences per step, positions by prefix sums, copies in dependency rounds  -> the output
 // Every loop is bounded by sizes read from the frame; every index into LDS or the workspace is checked against them.
+// The frame parsing of every stage is in zstd_dec_dev.h (dec_*), shared with the block-parallel form (zstd_dec_blocks.hip); this
+// file keeps what is its own: the three-wave pipeline, the tables and Huffman tree carried across blocks, the concrete repeat
+// offsets (pass 3), in-order execution, and the error codes.
 #include "zstd_dec_dev.h"
 #ifdef TSX_PROF2
 static unsigned long long* g_dprof_out = nullptr;                     // 8 u64 per chunk: phase laps of the decoder
@@ -58,28 +61,11 @@ __device__ __forceinline__ static void zstd_decompress_body(DecLds& L, const uin
     uint64_t contentSize = 0;
     uint32_t p = 0;
     bool hasChecksum = false, prodDone = false, fseDone = false, frameDone = false;
-    // ---- frame header ----
-    if (srcSize < 6) FAIL(DERR_FRAME);
-    if (src[0] != 0x28 || src[1] != 0xB5 || src[2] != 0x2F || src[3] != 0xFD) FAIL(DERR_FRAME);
-    {   const uint32_t fhd = src[4];
-        const uint32_t single = (fhd >> 5) & 1, dictFlag = fhd & 3, fcsFlag = fhd >> 6;
-        hasChecksum = (fhd >> 2) & 1;
-        if (fhd & 8) FAIL(DERR_FRAME);                                  // reserved bit
-        p = 5;
-        if (!single) { if (p >= srcSize) FAIL(DERR_FRAME); if ((src[p] >> 3) > 21) FAIL(DERR_FRAME); p++; }
-        const uint32_t dl = dictFlag == 0 ? 0 : dictFlag == 1 ? 1 : dictFlag == 2 ? 2 : 4;
-        if (p + dl > srcSize) FAIL(DERR_FRAME);
-        {   uint32_t dictId = 0; for (uint32_t i = 0; i < dl; i++) dictId |= (uint32_t)src[p + i] << (8 * i);
-            if (dictId) FAIL(DERR_FRAME); }                             // dictionaries are not supported (the reference uses none)
-        p += dl;
-        const uint32_t fl = fcsFlag == 0 ? single : fcsFlag == 1 ? 2 : fcsFlag == 2 ? 4 : 8;
-        if (fl == 0) FAIL(TSX_E_BAD_SIZE);                              // unknown content size: "Invalid decompressed size"
-        if (p + fl > srcSize) FAIL(DERR_FRAME);
-        for (uint32_t i = 0; i < fl; i++) contentSize |= (uint64_t)src[p + i] << (8 * i);
-        if (fl == 2) contentSize += 256;
-        p += fl;
+    {   const DecFrame fh = dec_frame_header(src, srcSize);
+        if (fh.status != TSX_OK) FAIL(fh.status);
+        if (fh.contentSize > d.dst_cap) FAIL(TSX_E_DST_TOO_SMALL);
+        p = fh.p; contentSize = fh.contentSize; hasChecksum = fh.hasChecksum;
     }
-    if (contentSize > d.dst_cap) FAIL(TSX_E_DST_TOO_SMALL);
     if (role == 0 && lane == 0) { L.hufValid = 0; L.llValid = 0; L.ofValid = 0; L.mlValid = 0; L.zeroEntry = 0; L.err = TSX_OK; }
     if (role == 0 && lane < 36) { L.cLLbase[lane] = dLLbase[lane]; L.cLLbits[lane] = dLLbits[lane]; }
     if (role == 0 && lane < 53) { L.cMLbase[lane] = dMLbase[lane]; L.cMLbits[lane] = dMLbits[lane]; }
@@ -97,46 +83,20 @@ __device__ __forceinline__ static void zstd_decompress_body(DecLds& L, const uin
             if (role == 1) {
                 if (!prodDone) {
                     uint8_t* const lit = litBuf[it % 3];
-                    if (p + 3 > srcSize) RFAIL(DERR_FRAME);
-                    const uint32_t bh = (uint32_t)src[p] | ((uint32_t)src[p + 1] << 8) | ((uint32_t)src[p + 2] << 16);
-                    p += 3;
-                    const uint32_t last = bh & 1, btype = (bh >> 1) & 3, bsize = bh >> 3;
-                    BlkDesc bd; bd.off = p; bd.bsize = bsize; bd.btype = btype; bd.last = last; bd.litInPlace = 0; bd.litOff = 0; bd.litSize = 0; bd.q = 0;
-                    if (btype == 0) { if (p + bsize > srcSize) RFAIL(DERR_FRAME); p += bsize; }
-                    else if (btype == 1) { if (p + 1 > srcSize) RFAIL(DERR_FRAME); p += 1; }
-                    else if (btype == 2) {
-                        if (bsize > ZS_BLOCK_MAX || p + bsize > srcSize || bsize < 2) RFAIL(DERR_FRAME);
-                        const uint8_t* const blk = src + p;
-                        const uint32_t b0 = blk[0], ltype = b0 & 3, sf = (b0 >> 2) & 3;
-                        uint32_t litSize = 0, q = 0;
-                        uint32_t litInPlace = 0, litOff = 0;
-                        if (ltype < 2) {
-                            uint32_t hl;
-                            if (sf == 0 || sf == 2) { litSize = b0 >> 3; hl = 1; }
-                            else if (sf == 1) { if (bsize < 2) RFAIL(DERR_FRAME); litSize = (b0 >> 4) + ((uint32_t)blk[1] << 4); hl = 2; }
-                            else { if (bsize < 3) RFAIL(DERR_FRAME); litSize = (b0 >> 4) + ((uint32_t)blk[1] << 4) + ((uint32_t)blk[2] << 12); hl = 3; }
-                            if (litSize > ZS_BLOCK_MAX) RFAIL(DERR_FRAME);
-                            if (ltype == 0) { if (hl + litSize > bsize) RFAIL(DERR_FRAME); litInPlace = 1; litOff = hl; q = hl + litSize; }
-                            else {
-                                if (hl + 1 > bsize) RFAIL(DERR_FRAME);
-                                const uint8_t b = blk[hl];
-                                for (uint32_t i = lane; i < litSize; i += LANES) lit[i] = b;
-                                q = hl + 1;
-                            }
-                        } else {
-                            uint32_t hl, bits, streams; uint64_t v = 0;
-                            if (sf == 0) { hl = 3; bits = 10; streams = 1; }
-                            else if (sf == 1) { hl = 3; bits = 10; streams = 4; }
-                            else if (sf == 2) { hl = 4; bits = 14; streams = 4; }
-                            else { hl = 5; bits = 18; streams = 4; }
-                            if (hl > bsize) RFAIL(DERR_FRAME);
-                            for (uint32_t i = 0; i < hl; i++) v |= (uint64_t)blk[i] << (8 * i);
-                            litSize = (uint32_t)(v >> 4) & ((1u << bits) - 1);
-                            const uint32_t csize = (uint32_t)(v >> (4 + bits)) & ((1u << bits) - 1);
-                            if (litSize > ZS_BLOCK_MAX || hl + csize > bsize || litSize == 0) RFAIL(DERR_FRAME);
-                            uint32_t t = hl;
-                            if (ltype == 2) {
-                                if (lane == 0) L.scalH[0] = huf_readTable(L, blk + hl, csize);
+                    const DecBlockHdr bh = dec_block_header(src, srcSize, p);
+                    if (!bh.ok) RFAIL(DERR_FRAME);
+                    p = bh.next;
+                    BlkDesc bd; bd.off = bh.off; bd.bsize = bh.bsize; bd.btype = bh.btype; bd.last = bh.last; bd.litInPlace = 0; bd.litOff = 0; bd.litSize = 0; bd.q = 0;
+                    if (bh.btype == 2) {
+                        const uint8_t* const blk = src + bh.off;
+                        const DecLit h = dec_lit_header(blk, bh.bsize);
+                        if (!h.section) RFAIL(DERR_FRAME);
+                        if (h.ltype == 0) { bd.litInPlace = 1; bd.litOff = h.hl; }
+                        else if (h.ltype == 1) { const uint8_t b = blk[h.hl]; for (uint32_t i = lane; i < h.litSize; i += LANES) lit[i] = b; }
+                        else {
+                            uint32_t t = h.hl;
+                            if (h.ltype == 2) {
+                                if (lane == 0) L.scalH[0] = huf_readTable(L, blk + h.hl, h.csize);
                                 WAVE_SYNC();
                                 const uint32_t used = L.scalH[0];
                                 WAVE_SYNC();
@@ -145,93 +105,12 @@ __device__ __forceinline__ static void zstd_decompress_body(DecLds& L, const uin
                                 WAVE_SYNC();
                                 t += used;
                             } else if (!L.hufValid) RFAIL(DERR_FRAME);
-                            const uint32_t payload = hl + csize - t;
-                            // stream layout
-                            uint32_t sOff[5], sCnt[4];
-                            if (streams == 1) { sOff[0] = 0; sOff[1] = payload; sCnt[0] = litSize; }
-                            else {
-                                if (payload < 10) RFAIL(DERR_FRAME);
-                                const uint32_t s1 = blk[t] | (blk[t + 1] << 8), s2 = blk[t + 2] | (blk[t + 3] << 8), s3 = blk[t + 4] | (blk[t + 5] << 8);
-                                if (6 + (uint64_t)s1 + s2 + s3 >= payload) RFAIL(DERR_FRAME);
-                                sOff[0] = 6; sOff[1] = 6 + s1; sOff[2] = sOff[1] + s2; sOff[3] = sOff[2] + s3; sOff[4] = payload;
-                                const uint32_t seg = (litSize + 3) / 4;
-                                if (3 * seg > litSize) RFAIL(DERR_FRAME);
-                                sCnt[0] = sCnt[1] = sCnt[2] = seg; sCnt[3] = litSize - 3 * seg;
-                            }
-                            // The (1 or 4) Huffman streams decode on lanes 0..3, each through its own LDS window of the stream, refilled by
-                            // the whole wave whenever a lane gets close to its window's lower edge (a reload from global memory would be a
-                            // dependent round trip every four symbols).
-                            bool ok = true;
-                            {
-                                const bool mine = lane < streams;
-                                uint32_t o = 0; for (uint32_t k = 0; k < lane && k < 4; k++) o += mine ? sCnt[k] : 0;
-                                const uint32_t cnt = mine ? sCnt[lane] : 0, sn = mine ? sOff[lane + 1] - sOff[lane] : 0, sbeg = mine ? t + sOff[lane] : 0;
-                                uint8_t* const outp = lit + o;
-                                // Bh = bits of the stream not read yet (cursor from the top; the last byte carries the end mark).  A step
-                                // decodes four symbols (<= 44 bits) from ONE 8-byte window read at the cursor, no branches inside; the last
-                                // symbols of a stream (fewer than four left, or fewer than 44 bits) go one at a time, with the bits below
-                                // the stream's first one read as zeros like libzstd's container does.
-                                uint32_t hi = 0, Bh = 0; bool hdone = !mine;
-                                if (mine) {
-                                    const uint32_t lastByte = sn ? blk[sbeg + sn - 1] : 0;
-                                    if (lastByte == 0) { ok = false; hdone = true; }
-                                    else Bh = 8 * (sn - 1) + dhb32(lastByte);
-                                }
-                                const uint32_t tableLog = L.hufLog, tmask = (1u << tableLog) - 1;
-                                for (;;) {
-                                    const uint32_t myTop = hdone ? 0 : (Bh >> 3) + 8;                                // bytes past the stream's end are zeros
-                                    const uint32_t myWb = myTop > ZS_HWIN ? (myTop - ZS_HWIN + 15) & ~15u : 0;     // top - wb <= ZS_HWIN = one 16-byte piece per lane
-                                    for (uint32_t s_ = 0; s_ < streams; s_++) {
-                                        const uint32_t top = (uint32_t)__builtin_amdgcn_readlane(myTop, (int)s_), wb = (uint32_t)__builtin_amdgcn_readlane(myWb, (int)s_), beg = (uint32_t)__builtin_amdgcn_readlane(sbeg, (int)s_), n_ = (uint32_t)__builtin_amdgcn_readlane(sn, (int)s_);
-                                        const uint32_t k = lane * 16;
-                                        if (wb + k < top) {
-                                            uint4 v;
-                                            if (wb + k + 16 <= n_) __builtin_memcpy(&v, blk + beg + wb + k, 16);
-                                            else { uint8_t tmp[16]; for (uint32_t j = 0; j < 16; j++) tmp[j] = wb + k + j < n_ ? blk[beg + wb + k + j] : 0; __builtin_memcpy(&v, tmp, 16); }
-                                            *reinterpret_cast<uint4*>(&L.hwin[s_ * (ZS_HWIN + 16) + k]) = v;
-                                        }
-                                    }
-                                    __threadfence_block();
-                                    WAVE_SYNC();
-                                    if (!hdone) {
-                                        const uint8_t* const win = &L.hwin[lane * (ZS_HWIN + 16)];
-                                        // five table reads per 8-byte window read: each yields the one to three symbols coded in the next 11 bits
-                                        while (hi + 16 <= cnt && Bh >= 56 && ((Bh - 56) >> 3) >= myWb) {
-                                            const uint32_t lo = Bh - 56;
-                                            const uint64_t c = wld64(win, myWb, lo >> 3) >> (lo & 7);               // bits [lo, lo + 56) of the stream
-                                            uint32_t used = 0;
-                                            #pragma unroll
-                                            for (int k = 0; k < 5; k++) {
-                                                const uint32_t e = L.hufX[(uint32_t)(c >> (45 - used)) & 0x7FF];
-                                                const uint32_t sy = e & 0xFFFFFF;                                  // one byte of slack behind the symbols
-                                                __builtin_memcpy(outp + hi, &sy, 4);
-                                                hi += e >> 28; used += (e >> 24) & 15;
-                                            }
-                                            Bh -= used;
-                                        }
-                                        while (hi < cnt && (hi + 16 > cnt || Bh < 56)) {                             // the stream's tail, one symbol at a time
-                                            const uint32_t need = Bh < tableLog ? Bh : tableLog, lo = Bh - need;
-                                            if ((lo >> 3) < myWb) break;                                             // behind the window: refill first
-                                            const uint32_t bits = (uint32_t)(wld64(win, myWb, lo >> 3) >> (lo & 7)) & ((1u << need) - 1);
-                                            const uint32_t e = huf_decode1(L, (bits << (tableLog - need)) & tmask, tableLog);
-                                            if ((e >> 8) > Bh) { ok = false; hdone = true; break; }                   // reads past the stream's first bit
-                                            outp[hi++] = (uint8_t)e; Bh -= e >> 8;
-                                        }
-                                        if (!hdone && hi >= cnt) { if (Bh != 0) ok = false; hdone = true; }           // every bit used, none missing
-                                    }
-                                    WAVE_SYNC();
-                                    if (__all(hdone)) break;
-                                }
-                            }
-                            if (__any(!ok)) RFAIL(DERR_FRAME);
-                            q = hl + csize;
+                            if (!dec_huf_streams(L, blk + t, h.section - t, h.streams, h.litSize, lit, lane)) RFAIL(DERR_FRAME);
                         }
-                        bd.litInPlace = litInPlace; bd.litOff = litOff; bd.litSize = litSize; bd.q = q;
-                        p += bsize;
-                    } else RFAIL(DERR_FRAME);
-                    if (last) {
-                        if (hasChecksum) { if (p + 4 > srcSize) RFAIL(DERR_FRAME); p += 4; }
-                        if (p != srcSize) RFAIL(DERR_FRAME);
+                        bd.litSize = h.litSize; bd.q = h.section;
+                    }
+                    if (bh.last) {
+                        if (!dec_frame_end(p, srcSize, hasChecksum)) RFAIL(DERR_FRAME);
                         prodDone = true;
                     }
                     if (lane == 0) L.desc[it % 3] = bd;
@@ -333,173 +212,38 @@ __device__ __forceinline__ static void zstd_decompress_body(DecLds& L, const uin
                 if (btype == 2) {
                     uint32_t* const sLL = (uint32_t*)seqBuf[(it - 1) & 1]; uint32_t* const sML = sLL + ZS_DSEQ_CAP; uint32_t* const sOF = sML + ZS_DSEQ_CAP;
                     const uint8_t* const blk = src + boff;
-                    uint32_t q = DUNI(bdp->q);
-                    if (q >= bsize) RFAIL(DERR_FRAME);
-                    uint32_t nbSeq = blk[q];
-                    if (nbSeq == 0) q += 1;
-                    else if (nbSeq < 128) q += 1;
-                    else if (nbSeq < 255) { if (q + 2 > bsize) RFAIL(DERR_FRAME); nbSeq = ((nbSeq - 128) << 8) + blk[q + 1]; q += 2; }
-                    else { if (q + 3 > bsize) RFAIL(DERR_FRAME); nbSeq = blk[q + 1] + ((uint32_t)blk[q + 2] << 8) + 0x7F00; q += 3; }
-                    nbSeq = DUNI(nbSeq);                                        // loaded through the vector path: pin it (and every loop bound derived from it) to SGPRs
-                    if (nbSeq > ZS_BLOCK_MAX / 3 + 1) RFAIL(DERR_FRAME);            // 128 KiB / minMatch 3 = 43691 at most in a valid block
+                    const DecSeqHdr sh = dec_seq_header(blk, bsize, DUNI(bdp->q));
+                    if (!sh.ok) RFAIL(DERR_FRAME);
+                    const uint32_t nbSeq = DUNI(sh.nbSeq);                      // loaded through the vector path: pin it (and every loop bound derived from it) to SGPRs
                     if (nbSeq) {
-                        // The three sequence tables (literal lengths, offsets, match lengths).  Lane 0 parses each table description
-                        // (a short serial bit parse); the decoding table itself is built by the whole wave (fse_buildSeqTable_wave).
-                        if (q >= bsize) RFAIL(DERR_FRAME);
-                        const uint32_t modes = DUNI(blk[q]);
-                        uint32_t t = q + 1;
-                        if (modes & 3) RFAIL(DERR_FRAME);
+                        // the three sequence tables (literal lengths, offsets, match lengths); a Repeat keeps the previous block's table
+                        const uint32_t modes = DUNI(sh.modes);
+                        uint32_t t = DUNI(sh.t);
                         for (int k = 0; k < 3; k++) {
                             const uint32_t mode = (modes >> (6 - 2 * k)) & 3;
-                            SeqD* const dt = k == 0 ? L.ll : k == 1 ? L.of : L.ml;
-                            uint32_t* const logp = k == 0 ? &L.llLog : k == 1 ? &L.ofLog : &L.mlLog;
                             int* const validp = k == 0 ? &L.llValid : k == 1 ? &L.ofValid : &L.mlValid;
-                            const uint32_t maxSymK = k == 0 ? 35 : k == 1 ? 31 : 52, maxLogK = k == 0 ? 9 : k == 1 ? 8 : 9;
-                            if (mode == 0) {                                    // predefined distribution
-                                const short* const dn = k == 0 ? dLLnorm : k == 1 ? dOFnorm : dMLnorm;
-                                const uint32_t dmax = k == 0 ? 35 : k == 1 ? 28 : 52, dlog = k == 1 ? 5 : 6;
-                                if (lane <= dmax) L.norm[lane] = dn[lane];
-                                if (lane == 0) { *logp = dlog; *validp = 1; }
-                                __threadfence_block();
-                                WAVE_SYNC();
-                                if (!fse_buildSeqTable_wave(dt, L, dmax, dlog, k, lane)) RFAIL(DERR_FRAME);
-                            } else if (mode == 1) {                             // RLE: one symbol, no state bits
-                                if (t >= bsize) RFAIL(DERR_FRAME);
-                                const uint32_t sym = DUNI(blk[t]);
-                                t++;
-                                if (sym > maxSymK) RFAIL(DERR_FRAME);
-                                if (lane == 0) { dt[0] = SEQD(0, 0, seq_ebits(L, sym, k), sym); *logp = 0; *validp = 1; }
-                            } else if (mode == 2) {                             // FSE-compressed distribution
-                                if (t >= bsize) RFAIL(DERR_FRAME);
-                                if (lane == 0) {
-                                    uint32_t ms = maxSymK, tl = 0;
-                                    const uint32_t used = fse_readNCount(L.norm, &ms, &tl, blk + t, bsize - t, maxLogK);
-                                    L.scal[0] = used; L.scal[3] = ms; L.scal[4] = tl;
-                                    if (used) { *logp = tl; *validp = 1; }
-                                }
-                                __threadfence_block();
-                                WAVE_SYNC();
-                                const uint32_t used = DUNI(L.scal[0]), ms = DUNI(L.scal[3]), tl = DUNI(L.scal[4]);
-                                if (!used || !fse_buildSeqTable_wave(dt, L, ms, tl, k, lane)) RFAIL(DERR_FRAME);
-                                t += used;
-                            } else {                                            // repeat the previous block's table
+                            if (mode == 3) {
                                 WAVE_SYNC();
                                 if (!*validp) RFAIL(DERR_FRAME);
+                                continue;
                             }
+                            const int32_t used = dec_seq_table(L, k, mode, blk + t, bsize - t, lane);
+                            if (used < 0) RFAIL(DERR_FRAME);
+                            if (lane == 0) *validp = 1;
+                            t += (uint32_t)used;
                         }
                         if (t >= bsize) RFAIL(DERR_FRAME);
-                        if (lane == 0) L.scal[2] = t;
                         __threadfence_block();
                         WAVE_SYNC();
                         DLT(1);                                                 // 1: sequence tables
-                    } else if (q != bsize) RFAIL(DERR_FRAME);
-                    // ---- decode and execute the sequences, 64 at a time (one per lane) ----
-                    // The sequence bit stream is one serial chain (read backwards; each FSE state transition says how many bits the
-                    // next one reads), staged through an LDS window that the whole wave refills.  Only the part of a sequence that IS
-                    // serial runs serially: pass 1 walks the three state machines for up to 64 sequences as wave-uniform scalar code
-                    // (three 4-byte table reads and one bit-window read per sequence) and drops each sequence's states and bit cursor
-                    // into its own lane (v_writelane); pass 2 lets every lane pull its sequence's extra bits out of the window and form
-                    // (literal length, match length, offset code) - all 64 at once; pass 3 resolves the repeat offsets in order (a short
-                    // uniform loop over lane values), which makes the execution below order-free.
-                    {
-                        const uint32_t llLog = DUNI(L.llLog), ofLog = DUNI(L.ofLog), mlLog = DUNI(L.mlLog);
-                        const uint8_t* const win = L.swin + ZS_DPAD;
-                        const uint8_t* stream = blk; uint32_t n = 0;
-                        uint32_t B = 0, wbase = 0, e = 0;                               // B: bits of the stream not read yet (the cursor, from the top)
-                        // lanes 0, 1, 2 = the LL, ML, OF state machines; the others carry state 0 through an all-zero entry
-                        const SeqD* const tbl = lane == 0 ? L.ll : lane == 1 ? L.ml : lane == 2 ? L.of : &L.zeroEntry;
-                        uint16_t* const recp = &L.rec[lane < 3 ? lane : 3];
-                        uint32_t st = 0;
-                        bool filled = false;
-                        if (nbSeq) {
-                            const uint32_t t = DUNI(L.scal[2]);
-                            n = DUNI(bsize - t); stream = blk + t;                  // n >= 1 (checked with the tables)
-                            const uint32_t lastByte = DUNI(stream[n - 1]);          // BIT_initDStream: the last byte carries the end mark
-                            if (lastByte == 0) RFAIL(DERR_FRAME);
-                            B = 8 * (n - 1) + dhb32(lastByte);
-                        }
+                        // ---- decode the sequences, 64 at a time (one per lane): passes 1 and 2 in dec_seq_group, pass 3 below ----
+                        DecSeqStream stream = {blk + t, DUNI(bsize - t), 0, 0, 0};
                         TSX_SETPRIO(3);                                         // the sequence stage is the chunk's critical path: its chain goes first
                         for (uint32_t g = 0; g < nbSeq; g += LANES) {
                             const uint32_t cnt = DUNI(nbSeq - g < LANES ? nbSeq - g : LANES);
-                            // 64 sequences read at most 64 * 89 bits = 712 bytes below the cursor; every read is an 8-byte load at
-                            // byte (bit >> 3), so the window holds [wbase, (B >> 3) + 8) with the bytes past the stream's end as zeros
-                            if (!filled || (wbase != 0 && (B >> 3) < wbase + 736)) {
-                                WAVE_SYNC();                                    // everyone is done with the previous window
-                                const uint32_t top = (B >> 3) + 8;
-                                wbase = top > ZS_DWIN ? (top - ZS_DWIN) & ~15u : 0;
-                                for (uint32_t k = lane * 16; wbase + k < top; k += LANES * 16) {
-                                    uint4 v;
-                                    if (wbase + k + 16 <= n) __builtin_memcpy(&v, stream + wbase + k, 16);
-                                    else { uint8_t tmp[16]; for (uint32_t j = 0; j < 16; j++) tmp[j] = wbase + k + j < n ? stream[wbase + k + j] : 0; __builtin_memcpy(&v, tmp, 16); }
-                                    *reinterpret_cast<uint4*>(&L.swin[ZS_DPAD + k]) = v;
-                                }
-                                if (lane < ZS_DPAD / 4) reinterpret_cast<uint32_t*>(L.swin)[lane] = 0;      // the margin in front of the window
-                                __threadfence_block();
-                                WAVE_SYNC();
-                                if (!filled) {                                      // initial states: LL, OF, ML (ZSTD_initFseState order)
-                                    filled = true;
-                                    const uint32_t lo = B - (llLog + ofLog + mlLog);              // <= 26 bits
-                                    if ((int32_t)lo < 0) RFAIL(DERR_FRAME);
-                                    const uint32_t w = DUNI((uint32_t)(wld64(win, wbase, lo >> 3) >> (lo & 7)));
-                                    const uint32_t sm = w & ((1u << mlLog) - 1), so = (w >> mlLog) & ((1u << ofLog) - 1), sl = (w >> (mlLog + ofLog)) & ((1u << llLog) - 1);
-                                    st = lane == 0 ? sl : lane == 1 ? sm : lane == 2 ? so : 0;
-                                    B = lo;
-                                }
-                            }
-                            // pass 1: the chain, on the vector unit.  Lanes 0, 1, 2 run the LL, ML and OF state machines (that is the order
-                            // in which a sequence's state-update bits sit in the stream, highest first); one table read serves all three,
-                            // two DPP adds give every machine the bits below its own field and lane 0 the sequence's bit total, and the
-                            // 8 bytes that hold the update bits are read together with the entries from the cursor alone ([B - 56.., B));
-                            // only a sequence that reads more than 56 bits needs a second, dependent read.  The scalar unit - ONE per CU,
-                            // shared by every wave - keeps just the cursor and the loop.  The states go to LDS (rec) for pass 2; an
-                            // over-read shows as a negative cursor (collected in `bad`, checked once per group) and is clamped so that no
-                            // load leaves the window.  The last sequence of a block reads no update bits: peeled off the loop.
-                            uint32_t bad = 0;
-                            const uint32_t Bgroup = B;
-                            const uint32_t upd = g + cnt < nbSeq ? cnt : cnt - 1;
-                            uint32_t j = 0;
-                            for (; j + 2 <= upd; j += 2) {                                    // two steps per trip: rec offsets become immediates, half the loop control
-                                seq_chain_step(tbl, recp + j * 4, win, wbase, st, B, bad);
-                                seq_chain_step(tbl, recp + j * 4 + 4, win, wbase, st, B, bad);
-                            }
-                            if (j < upd) seq_chain_step(tbl, recp + j * 4, win, wbase, st, B, bad);
-                            if (upd < cnt) {
-                                const uint32_t e_ = tbl[st];
-                                recp[upd * 4] = (uint16_t)st;
-                                const uint32_t eb = SEQD_EBITS(e_);
-                                const int32_t raw = (int32_t)(B - DUNI(eb + DPP_SHL(eb, 1) + DPP_SHL(eb, 2)));
-                                bad |= (uint32_t)raw;
-                                B = (uint32_t)(raw < 0 ? 0 : raw);
-                            }
-                            e = bad >> 31;
-                            if (e) RFAIL(DERR_FRAME);                                // the stream is shorter than its sequences need
-                            __threadfence_block();
-                            WAVE_SYNC();
-                            // pass 2: every lane decodes the fields of its own sequence from the window; its cursor is the group's minus
-                            // the bits of the sequences before it (prefix sum)
+                            uint32_t ll, ml, offBase;
+                            if (!dec_seq_group(L, stream, g, cnt, nbSeq, lane, ll, ml, offBase)) RFAIL(DERR_FRAME);
                             const bool valid = lane < cnt;
-                            uint32_t ll = 0, ml = 0, offBase = 4;
-                            {
-                                uint32_t el = 0, eo = 0, em = 0, mine = 0;
-                                if (valid) {
-                                    uint64_t r; __builtin_memcpy(&r, &L.rec[lane * 4], 8);
-                                    el = L.ll[(uint32_t)r & 0xFFFF]; em = L.ml[(uint32_t)(r >> 16) & 0xFFFF]; eo = L.of[(uint32_t)(r >> 32) & 0xFFFF];
-                                    mine = SEQD_TOT(el) + SEQD_TOT(eo) + SEQD_TOT(em);
-                                    if (g + lane + 1 == nbSeq) mine = SEQD_EBITS(el) + SEQD_EBITS(eo) + SEQD_EBITS(em);
-                                }
-                                uint32_t incl = mine;
-                                for (uint32_t o = 1; o < LANES; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if (lane >= o) incl += v; }
-                                if (valid) {
-                                    const uint32_t oc = SEQD_EBITS(eo), mbits = SEQD_EBITS(em), lbits = SEQD_EBITS(el);
-                                    const uint32_t lbase = L.cLLbase[SEQD_SYM(el)], mbase = L.cMLbase[SEQD_SYM(em)];
-                                    const uint32_t lo1 = Bgroup - (incl - mine) - oc;           // offset bits first (<= 31), then ML, then LL (<= 16 each)
-                                    offBase = (1u << oc) + ((uint32_t)(wld64(win, wbase, lo1 >> 3) >> (lo1 & 7)) & ((1u << oc) - 1));
-                                    const uint32_t lo2 = lo1 - mbits - lbits;
-                                    const uint32_t w2 = (uint32_t)(wld64(win, wbase, lo2 >> 3) >> (lo2 & 7));
-                                    ll = lbase + (w2 & ((1u << lbits) - 1));
-                                    ml = mbase + ((w2 >> lbits) & ((1u << mbits) - 1));
-                                }
-                            }
                             // pass 3: repeat offsets.  A sequence with a new offset (code > 3) knows it already and only pushes it onto the
                             // history; the scalar loop visits just the sequences that USE the history (codes 1..3), in order, first
                             // folding in the new offsets pushed since the previous visit (only the last three matter).  Code c names
@@ -539,7 +283,7 @@ __device__ __forceinline__ static void zstd_decompress_body(DecLds& L, const uin
                             DLT(2);                                                 // 2: FSE sequence decode
                         }
                         TSX_SETPRIO(0);
-                        if (nbSeq && B != 0) RFAIL(DERR_FRAME);                     // BIT_endOfDStream: every bit of the stream was used
+                        if (stream.B != 0) RFAIL(DERR_FRAME);                      // BIT_endOfDStream: every bit of the stream was used
                     }
                     if (lane == 0) L.nseq[(it - 1) & 1] = nbSeq;
                 }

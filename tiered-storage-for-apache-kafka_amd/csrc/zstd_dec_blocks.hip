@@ -8,8 +8,8 @@
 //                      and sequence arenas and notes which earlier block holds the Huffman tree (treeless literals) and the FSE
 //                      tables (Repeat mode) in force.
 //   zb_decode_kernel   one workgroup (two waves) per block, all blocks of all chunks at once.  Wave 1 decodes the literals, wave 0
-//                      the sequences - the same stages as zstd_dec.hip's (11-bit multi-symbol Huffman table, the three FSE state
-//                      machines in lanes 0-2, field extraction on all lanes) - but a block that inherits a tree or a table rebuilds
+//                      the sequences - through the same stage helpers as zstd_dec.hip (zstd_dec_dev.h: 11-bit multi-symbol Huffman
+//                      table, the three FSE state machines in lanes 0-2, field extraction on all lanes) - but a block that inherits a tree or a table rebuilds
 //                      it from the earlier block's bytes, and repeat offsets are resolved SYMBOLICALLY: a block does not know the
 //                      history it starts from, so an offset that comes out of the history is recorded as "incoming entry i minus d"
 //                      and the block's outgoing history is a function of the incoming one.
@@ -25,7 +25,9 @@
 // This form is a fast path, not a second authority: anything it does not like (more than 264 blocks, a chunk above 16 MiB, a
 // malformed frame, an offset out of range, a copy chain that does not end in a literal) clears the chunk's `mode` word and zstd_decompress_kernel - which
 // is launched behind it with that word as its skip list - decodes the chunk and reports the error code.  Bytes are either final
-// and correct or rewritten by the fallback.
+// and correct or rewritten by the fallback.  Both forms parse frame bytes through the same helpers (zstd_dec_dev.h, dec_*), so
+// they read every frame alike; this file adds only the limits of its own (ZB_MAX_BLOCKS, ZB_MAX_CHUNK, raw / RLE blocks of at most
+// Block_Maximum_Size, offsets below 2^31, the per-block regenerated sizes), each of which hands the chunk back.
 #include "zstd_dec_dev.h"
 #include "zstd_dec_blocks.h"
 #ifdef ZB_DEBUG
@@ -51,37 +53,6 @@ __device__ static inline uint32_t zb_subst(uint32_t v, uint32_t h0, uint32_t h1,
     return r - ZB_SYM_DEC(v);                                           // 0 or wrapped when the frame is corrupt: caught where it is used
 }
 
-// literals-section header of a compressed block -> section size (0 = malformed)
-struct ZbLit { uint32_t ltype, hl, litSize, csize, streams, section; };
-__device__ static inline ZbLit zb_lit_header(const uint8_t* blk, uint32_t bsize) {
-    ZbLit h; h.section = 0; h.csize = 0; h.streams = 1;
-    const uint32_t b0 = blk[0], sf = (b0 >> 2) & 3;
-    h.ltype = b0 & 3;
-    if (h.ltype < 2) {
-        if (sf == 0 || sf == 2) { h.litSize = b0 >> 3; h.hl = 1; }
-        else if (sf == 1) { if (bsize < 2) return h; h.litSize = (b0 >> 4) + ((uint32_t)blk[1] << 4); h.hl = 2; }
-        else { if (bsize < 3) return h; h.litSize = (b0 >> 4) + ((uint32_t)blk[1] << 4) + ((uint32_t)blk[2] << 12); h.hl = 3; }
-        if (h.litSize > ZS_BLOCK_MAX) return h;
-        const uint32_t sec = h.ltype == 0 ? h.hl + h.litSize : h.hl + 1;
-        if (sec > bsize) return h;
-        h.section = sec;
-    } else {
-        uint32_t bits;
-        if (sf == 0) { h.hl = 3; bits = 10; h.streams = 1; }
-        else if (sf == 1) { h.hl = 3; bits = 10; h.streams = 4; }
-        else if (sf == 2) { h.hl = 4; bits = 14; h.streams = 4; }
-        else { h.hl = 5; bits = 18; h.streams = 4; }
-        if (h.hl > bsize) return h;
-        uint64_t v = 0;
-        for (uint32_t i = 0; i < h.hl; i++) v |= (uint64_t)blk[i] << (8 * i);
-        h.litSize = (uint32_t)(v >> 4) & ((1u << bits) - 1);
-        h.csize = (uint32_t)(v >> (4 + bits)) & ((1u << bits) - 1);
-        if (h.litSize > ZS_BLOCK_MAX || h.hl + h.csize > bsize || h.litSize == 0) return h;
-        h.section = h.hl + h.csize;
-    }
-    return h;
-}
-
 // ---------------------------------------------------------------------------------------------------
 // index: one wave per chunk
 // ---------------------------------------------------------------------------------------------------
@@ -104,40 +75,19 @@ __global__ __launch_bounds__(LANES) void zb_index_kernel(const uint8_t* __restri
         // every early return below leaves mode = 0: the chunk-serial kernel decodes the chunk (and owns the error codes)
         uint32_t n = 0, bad = 1;
         do {
-            if (srcSize < 6 || d.dst_cap > ZB_MAX_CHUNK) break;
-            if (src[0] != 0x28 || src[1] != 0xB5 || src[2] != 0x2F || src[3] != 0xFD) break;
-            const uint32_t fhd = src[4], single = (fhd >> 5) & 1, dictFlag = fhd & 3, fcsFlag = fhd >> 6;
-            const bool hasChecksum = (fhd >> 2) & 1;
-            if (fhd & 8) break;
-            uint32_t p = 5;
-            if (!single) { if (p >= srcSize || (src[p] >> 3) > 21) break; p++; }
-            const uint32_t dl = dictFlag == 0 ? 0 : dictFlag == 1 ? 1 : dictFlag == 2 ? 2 : 4;
-            if (p + dl > srcSize) break;
-            uint32_t dictId = 0; for (uint32_t i = 0; i < dl; i++) dictId |= (uint32_t)src[p + i] << (8 * i);
-            if (dictId) break;
-            p += dl;
-            const uint32_t fl = fcsFlag == 0 ? single : fcsFlag == 1 ? 2 : fcsFlag == 2 ? 4 : 8;
-            if (fl == 0 || p + fl > srcSize) break;
-            uint64_t contentSize = 0;
-            for (uint32_t i = 0; i < fl; i++) contentSize |= (uint64_t)src[p + i] << (8 * i);
-            if (fl == 2) contentSize += 256;
-            p += fl;
-            if (contentSize > d.dst_cap) break;
-            C->contentSize = (uint32_t)contentSize;
+            if (d.dst_cap > ZB_MAX_CHUNK) break;
+            const DecFrame fh = dec_frame_header(src, srcSize);
+            if (fh.status != TSX_OK || fh.contentSize > d.dst_cap) break;
+            C->contentSize = (uint32_t)fh.contentSize;
+            uint32_t p = fh.p;
             bool closed = false;
             while (n < ZB_MAX_BLOCKS) {                                 // the chain of block headers
-                if (p + 3 > srcSize) break;
-                const uint32_t bh = (uint32_t)src[p] | ((uint32_t)src[p + 1] << 8) | ((uint32_t)src[p + 2] << 16);
-                p += 3;
-                const uint32_t last = bh & 1, btype = (bh >> 1) & 3, bsize = bh >> 3;
-                if (btype == 3) break;
-                if (btype == 2 && (bsize > ZS_BLOCK_MAX || bsize < 2)) break;
-                if (btype != 2 && bsize > ZS_BLOCK_MAX) break;         // a raw / RLE block regenerates Block_Size bytes: <= Block_Maximum_Size
-                const uint32_t body = btype == 1 ? 1 : bsize;
-                if (p + body > srcSize) break;
-                sOff[n] = p; sSize[n] = bsize; sType[n] = (uint8_t)(btype | (last << 2));
-                n++; p += body;
-                if (last) { if (hasChecksum) { if (p + 4 > srcSize) break; p += 4; } closed = p == srcSize; break; }
+                const DecBlockHdr bh = dec_block_header(src, srcSize, p);
+                if (!bh.ok) break;
+                if (bh.btype != 2 && bh.bsize > ZS_BLOCK_MAX) break;   // a raw / RLE block regenerates Block_Size bytes: <= Block_Maximum_Size
+                sOff[n] = bh.off; sSize[n] = bh.bsize; sType[n] = (uint8_t)(bh.btype | (bh.last << 2));
+                n++; p = bh.next;
+                if (bh.last) { closed = dec_frame_end(p, srcSize, fh.hasChecksum); break; }
             }
             if (closed) bad = 0;
         } while (0);
@@ -155,47 +105,32 @@ __global__ __launch_bounds__(LANES) void zb_index_kernel(const uint8_t* __restri
         bool bad = false;
         if (B.btype == 2) {
             const uint8_t* const blk = src + B.off;
-            const ZbLit h = zb_lit_header(blk, B.bsize);
-            if (!h.section) bad = true;
+            const DecLit h = dec_lit_header(blk, B.bsize);
+            const DecSeqHdr sh = h.section ? dec_seq_header(blk, B.bsize, h.section) : DecSeqHdr{0, 0, 0, 0};
+            if (!sh.ok) bad = true;
             else {
-                B.ltype = (uint8_t)h.ltype; B.litSize = h.litSize; B.q = h.section;
-                uint32_t q = h.section;
-                if (q >= B.bsize) bad = true;
-                else {
-                    uint32_t nbSeq = blk[q];
-                    if (nbSeq < 128) q += 1;
-                    else if (nbSeq < 255) { if (q + 2 > B.bsize) bad = true; else { nbSeq = ((nbSeq - 128) << 8) + blk[q + 1]; q += 2; } }
-                    else { if (q + 3 > B.bsize) bad = true; else { nbSeq = blk[q + 1] + ((uint32_t)blk[q + 2] << 8) + 0x7F00; q += 3; } }
-                    if (!bad && nbSeq > ZS_BLOCK_MAX / 3 + 1) bad = true;
-                    B.nbSeq = nbSeq;
-                    if (!bad && nbSeq == 0 && q != B.bsize) bad = true;
-                    if (!bad && nbSeq) {
-                        if (q >= B.bsize) bad = true;
-                        else {
-                            const uint32_t modes = blk[q];
-                            uint32_t t = q + 1;
-                            if (modes & 3) bad = true;
-                            B.modes = (uint8_t)modes;
-                            // (unrolled: B stays in registers - a dynamic index into B.tOff would put the whole struct into scratch, and no
-                            //  kernel on the fetch path may use scratch: see zstd_dec.hip, zstd_decompress_fallback_kernel)
+                B.ltype = (uint8_t)h.ltype; B.litSize = h.litSize; B.q = h.section; B.nbSeq = sh.nbSeq; B.modes = (uint8_t)sh.modes;
+                if (sh.nbSeq) {
+                    // where each table description defined here starts, and the bit stream behind them (the tables themselves are
+                    // built by the decode kernel).  Unrolled: B stays in registers - a dynamic index into B.tOff would put the whole
+                    // struct into scratch, and no kernel on the fetch path may use scratch: see zstd_dec.hip, zstd_decompress_fallback_kernel
+                    uint32_t t = sh.t;
 #pragma unroll
-                            for (int k = 0; k < 3; k++) {
-                                if (bad) continue;
-                                const uint32_t mode = (modes >> (6 - 2 * k)) & 3;
-                                const uint32_t maxSymK = k == 0 ? 35 : k == 1 ? 31 : 52, maxLogK = k == 0 ? 9 : k == 1 ? 8 : 9;
-                                B.tOff[k] = t;
-                                if (mode == 1) { if (t >= B.bsize) bad = true; t++; }
-                                else if (mode == 2) {
-                                    if (t >= B.bsize) { bad = true; continue; }
-                                    const uint32_t used = fse_skipNCount(maxSymK, blk + t, B.bsize - t, maxLogK);
-                                    if (!used) bad = true;
-                                    t += used;
-                                }
-                            }
-                            if (!bad && t >= B.bsize) bad = true;
-                            B.streamOff = t;
+                    for (int k = 0; k < 3; k++) {
+                        if (bad) continue;
+                        const uint32_t mode = (sh.modes >> (6 - 2 * k)) & 3;
+                        const uint32_t maxSymK = k == 0 ? 35 : k == 1 ? 31 : 52, maxLogK = k == 0 ? 9 : k == 1 ? 8 : 9;
+                        B.tOff[k] = t;
+                        if (mode == 1) { if (t >= B.bsize) bad = true; t++; }
+                        else if (mode == 2) {
+                            if (t >= B.bsize) { bad = true; continue; }
+                            const uint32_t used = fse_skipNCount(maxSymK, blk + t, B.bsize - t, maxLogK);
+                            if (!used) bad = true;
+                            t += used;
                         }
                     }
+                    if (!bad && t >= B.bsize) bad = true;
+                    B.streamOff = t;
                 }
             }
         }
@@ -242,116 +177,6 @@ extern "C" void tsx_debug_set_zbprof(void* dev_ptr) { g_zbprof_out = (unsigned l
 #define ZLT(k) do {} while (0)
 #endif
 
-// The 1 or 4 Huffman streams of a literals section, on lanes 0-3 through per-stream LDS windows (zstd_dec.hip's literal stage):
-// payload = the section's bytes behind the tree description.  Returns false (wave-uniform) on a malformed stream.
-__device__ static bool zb_huf_streams(DecLds& L, const uint8_t* __restrict__ pay, uint32_t payload, uint32_t streams, uint32_t litSize, uint8_t* __restrict__ lit, uint32_t lane) {
-    uint32_t sOff[5], sCnt[4];
-    if (streams == 1) { sOff[0] = 0; sOff[1] = payload; sOff[2] = sOff[3] = sOff[4] = payload; sCnt[0] = litSize; sCnt[1] = sCnt[2] = sCnt[3] = 0; }
-    else {
-        if (payload < 10) return false;
-        const uint32_t s1 = pay[0] | (pay[1] << 8), s2 = pay[2] | (pay[3] << 8), s3 = pay[4] | (pay[5] << 8);
-        if (6 + (uint64_t)s1 + s2 + s3 >= payload) return false;
-        sOff[0] = 6; sOff[1] = 6 + s1; sOff[2] = sOff[1] + s2; sOff[3] = sOff[2] + s3; sOff[4] = payload;
-        const uint32_t seg = (litSize + 3) / 4;
-        if (3 * seg > litSize) return false;
-        sCnt[0] = sCnt[1] = sCnt[2] = seg; sCnt[3] = litSize - 3 * seg;
-    }
-    bool ok = true;
-    const bool mine = lane < streams;
-    uint32_t o = 0; for (uint32_t k = 0; k < lane && k < 4; k++) o += mine ? sCnt[k] : 0;
-    const uint32_t cnt = mine ? sCnt[lane] : 0, sn = mine ? sOff[lane + 1] - sOff[lane] : 0, sbeg = mine ? sOff[lane] : 0;
-    uint8_t* const outp = lit + o;
-    uint32_t hi = 0, Bh = 0; bool hdone = !mine;
-    if (mine) {
-        const uint32_t lastByte = sn ? pay[sbeg + sn - 1] : 0;
-        if (lastByte == 0) { ok = false; hdone = true; }
-        else Bh = 8 * (sn - 1) + dhb32(lastByte);
-    }
-    const uint32_t tableLog = L.hufLog, tmask = (1u << tableLog) - 1;
-    for (;;) {
-        const uint32_t myTop = hdone ? 0 : (Bh >> 3) + 8;
-        const uint32_t myWb = myTop > ZS_HWIN ? (myTop - ZS_HWIN + 15) & ~15u : 0;
-        for (uint32_t s_ = 0; s_ < streams; s_++) {
-            const uint32_t top = (uint32_t)__builtin_amdgcn_readlane(myTop, (int)s_), wb = (uint32_t)__builtin_amdgcn_readlane(myWb, (int)s_), beg = (uint32_t)__builtin_amdgcn_readlane(sbeg, (int)s_), n_ = (uint32_t)__builtin_amdgcn_readlane(sn, (int)s_);
-            const uint32_t k = lane * 16;
-            if (wb + k < top) {
-                uint4 v;
-                if (wb + k + 16 <= n_) __builtin_memcpy(&v, pay + beg + wb + k, 16);
-                else { uint8_t tmp[16]; for (uint32_t j = 0; j < 16; j++) tmp[j] = wb + k + j < n_ ? pay[beg + wb + k + j] : 0; __builtin_memcpy(&v, tmp, 16); }
-                *reinterpret_cast<uint4*>(&L.hwin[s_ * (ZS_HWIN + 16) + k]) = v;
-            }
-        }
-        __threadfence_block();
-        WAVE_SYNC();
-        if (!hdone) {
-            const uint8_t* const win = &L.hwin[lane * (ZS_HWIN + 16)];
-            while (hi + 16 <= cnt && Bh >= 56 && ((Bh - 56) >> 3) >= myWb) {
-                const uint32_t lo = Bh - 56;
-                const uint64_t c = wld64(win, myWb, lo >> 3) >> (lo & 7);
-                uint32_t used = 0;
-                #pragma unroll
-                for (int k = 0; k < 5; k++) {
-                    const uint32_t e = L.hufX[(uint32_t)(c >> (45 - used)) & 0x7FF];
-                    const uint32_t sy = e & 0xFFFFFF;
-                    __builtin_memcpy(outp + hi, &sy, 4);
-                    hi += e >> 28; used += (e >> 24) & 15;
-                }
-                Bh -= used;
-            }
-            while (hi < cnt && (hi + 16 > cnt || Bh < 56)) {
-                const uint32_t need = Bh < tableLog ? Bh : tableLog, lo = Bh - need;
-                if ((lo >> 3) < myWb) break;
-                const uint32_t bits = (uint32_t)(wld64(win, myWb, lo >> 3) >> (lo & 7)) & ((1u << need) - 1);
-                const uint32_t e = huf_decode1(L, (bits << (tableLog - need)) & tmask, tableLog);
-                if ((e >> 8) > Bh) { ok = false; hdone = true; break; }
-                outp[hi++] = (uint8_t)e; Bh -= e >> 8;
-            }
-            if (!hdone && hi >= cnt) { if (Bh != 0) ok = false; hdone = true; }
-        }
-        WAVE_SYNC();
-        if (__all(hdone)) break;
-    }
-    return !__any(!ok);
-}
-
-// One of the three sequence tables of a block from its description: mode 0 predefined, 1 RLE, 2 FSE-compressed (never 3 here: the
-// caller has followed a Repeat back to the block that defines the table).  desc / avail: the description's bytes.
-__device__ static bool zb_seq_table(DecLds& L, int k, uint32_t mode, const uint8_t* __restrict__ desc, uint32_t avail, uint32_t lane) {
-    SeqD* const dt = k == 0 ? L.ll : k == 1 ? L.of : L.ml;
-    uint32_t* const logp = k == 0 ? &L.llLog : k == 1 ? &L.ofLog : &L.mlLog;
-    const uint32_t maxSymK = k == 0 ? 35 : k == 1 ? 31 : 52, maxLogK = k == 0 ? 9 : k == 1 ? 8 : 9;
-    if (mode == 0) {
-        const short* const dn = k == 0 ? dLLnorm : k == 1 ? dOFnorm : dMLnorm;
-        const uint32_t dmax = k == 0 ? 35 : k == 1 ? 28 : 52, dlog = k == 1 ? 5 : 6;
-        if (lane <= dmax) L.norm[lane] = dn[lane];
-        if (lane == 0) *logp = dlog;
-        __threadfence_block();
-        WAVE_SYNC();
-        return fse_buildSeqTable_wave(dt, L, dmax, dlog, k, lane);
-    }
-    if (mode == 1) {
-        if (avail < 1) return false;
-        const uint32_t sym = DUNI(desc[0]);
-        if (sym > maxSymK) return false;
-        if (lane == 0) { dt[0] = SEQD(0, 0, seq_ebits(L, sym, k), sym); *logp = 0; }
-        __threadfence_block();
-        WAVE_SYNC();
-        return true;
-    }
-    if (avail < 1) return false;
-    if (lane == 0) {
-        uint32_t ms = maxSymK, tl = 0;
-        const uint32_t used = fse_readNCount(L.norm, &ms, &tl, desc, avail, maxLogK);
-        L.scal[0] = used; L.scal[3] = ms; L.scal[4] = tl;
-        if (used) *logp = tl;
-    }
-    __threadfence_block();
-    WAVE_SYNC();
-    const uint32_t used = DUNI(L.scal[0]), ms = DUNI(L.scal[3]), tl = DUNI(L.scal[4]);
-    WAVE_SYNC();
-    return used && fse_buildSeqTable_wave(dt, L, ms, tl, k, lane);
-}
-
 __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __restrict__ frames, int from_mid, uint64_t mid_stride,
                                                               const tsx_chunk_desc* __restrict__ descs, uint8_t* __restrict__ hdrs, uint8_t* __restrict__ arenas,
                                                               uint64_t astride, uint32_t lit_cap, uint32_t seq_cap
@@ -376,7 +201,7 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
     const uint32_t bsize = DUNI(B->bsize);
     if (role == 1) {
         // ---- literals ----
-        const ZbLit h = zb_lit_header(blk, bsize);                      // (validated by the index kernel)
+        const DecLit h = dec_lit_header(blk, bsize);                      // (validated by the index kernel)
         if (h.ltype == 0) return;                                       // raw literals are read in place
         uint8_t* const lit = litArena + DUNI(B->litAt);
         if (h.ltype == 1) { const uint8_t v = blk[h.hl]; for (uint32_t i = lane; i < h.litSize; i += LANES) lit[i] = v; return; }
@@ -385,7 +210,7 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
         if (h.ltype == 3) {                                             // treeless: the tree of the latest block that carried one
             const ZbBlock* const S = &C->blk[DUNI(B->hufSrc)];
             const uint8_t* const sblk = src + DUNI(S->off);
-            const ZbLit sh = zb_lit_header(sblk, DUNI(S->bsize));
+            const DecLit sh = dec_lit_header(sblk, DUNI(S->bsize));
             if (sh.ltype != 2 || !sh.section) ZB_FAIL();
             tree = sblk + sh.hl; treeAvail = sh.csize;
         }
@@ -401,7 +226,7 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
         ZLT(6);
         if (h.ltype == 2) t += used;
         if (t > h.hl + h.csize) ZB_FAIL();
-        if (!zb_huf_streams(L, blk + t, h.hl + h.csize - t, h.streams, h.litSize, lit, lane)) ZB_FAIL();
+        if (!dec_huf_streams(L, blk + t, h.hl + h.csize - t, h.streams, h.litSize, lit, lane)) ZB_FAIL();
         ZLT(7);
 #ifdef TSX_PROF2
         if (lane == 0 && zbprof) { unsigned long long* const zp = zbprof + ((size_t)chunk * ZB_MAX_BLOCKS + b) * 8; zp[6] = zlt_[6]; zp[7] = zlt_[7]; }
@@ -420,98 +245,21 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
         const ZbBlock* const S = &C->blk[DUNI(B->tblSrc[k])];           // this block itself unless the table is a Repeat
         const uint32_t mode = (DUNI(S->modes) >> (6 - 2 * k)) & 3, to = DUNI(S->tOff[k]), sb = DUNI(S->bsize);
         if (mode == 3 || to > sb) ZB_FAIL();
-        if (!zb_seq_table(L, k, mode, src + DUNI(S->off) + to, sb - to, lane)) ZB_FAIL();
+        if (dec_seq_table(L, k, mode, src + DUNI(S->off) + to, sb - to, lane) < 0) ZB_FAIL();
     }
     ZLT(0);
     uint32_t* const sLL = seqArena + DUNI(B->seqAt); uint32_t* const sML = sLL + seq_cap; uint32_t* const sOF = sML + seq_cap;
-    const uint32_t llLog = DUNI(L.llLog), ofLog = DUNI(L.ofLog), mlLog = DUNI(L.mlLog);
-    const uint8_t* const win = L.swin + ZS_DPAD;
     const uint32_t t = DUNI(B->streamOff);
-    const uint32_t n = bsize - t;                                       // >= 1 (index kernel)
-    const uint8_t* const stream = blk + t;
-    const uint32_t lastByte = DUNI(stream[n - 1]);
-    if (lastByte == 0) ZB_FAIL();
-    uint32_t Bc = 8 * (n - 1) + dhb32(lastByte), wbase = 0;             // bits of the stream not read yet
-    const SeqD* const tbl = lane == 0 ? L.ll : lane == 1 ? L.ml : lane == 2 ? L.of : &L.zeroEntry;
-    uint16_t* const recp = &L.rec[lane < 3 ? lane : 3];
-    uint32_t st = 0;
-    bool filled = false;
+    DecSeqStream stream = {blk + t, bsize - t, 0, 0, 0};                // n >= 1 (index kernel)
     uint32_t r0 = ZB_SYM, r1 = ZB_SYM | (1u << 28), r2 = ZB_SYM | (2u << 28);      // the history this block starts from, whatever it is
     uint32_t sumLL = 0, sumML = 0;
     for (uint32_t g = 0; g < nbSeq; g += LANES) {
         const uint32_t cnt = DUNI(nbSeq - g < LANES ? nbSeq - g : LANES);
-        if (!filled || (wbase != 0 && (Bc >> 3) < wbase + 736)) {
-            WAVE_SYNC();
-            const uint32_t top = (Bc >> 3) + 8;
-            wbase = top > ZS_DWIN ? (top - ZS_DWIN) & ~15u : 0;
-            for (uint32_t k = lane * 16; wbase + k < top; k += LANES * 16) {
-                uint4 v;
-                if (wbase + k + 16 <= n) __builtin_memcpy(&v, stream + wbase + k, 16);
-                else { uint8_t tmp[16]; for (uint32_t j = 0; j < 16; j++) tmp[j] = wbase + k + j < n ? stream[wbase + k + j] : 0; __builtin_memcpy(&v, tmp, 16); }
-                *reinterpret_cast<uint4*>(&L.swin[ZS_DPAD + k]) = v;
-            }
-            if (lane < ZS_DPAD / 4) reinterpret_cast<uint32_t*>(L.swin)[lane] = 0;      // the margin in front of the window
-            __threadfence_block();
-            WAVE_SYNC();
-            if (!filled) {
-                filled = true;
-                const uint32_t lo = Bc - (llLog + ofLog + mlLog);
-                if ((int32_t)lo < 0) ZB_FAIL();
-                const uint32_t w = DUNI((uint32_t)(wld64(win, wbase, lo >> 3) >> (lo & 7)));
-                const uint32_t sm = w & ((1u << mlLog) - 1), so = (w >> mlLog) & ((1u << ofLog) - 1), sl = (w >> (mlLog + ofLog)) & ((1u << llLog) - 1);
-                st = lane == 0 ? sl : lane == 1 ? sm : lane == 2 ? so : 0;
-                Bc = lo;
-            }
-        }
-        ZLT(1);
-        // pass 1: the chain (lanes 0, 1, 2 = the LL, ML, OF state machines; see zstd_dec.hip)
-        uint32_t bad = 0;
-        const uint32_t Bgroup = Bc;
-        const uint32_t upd = g + cnt < nbSeq ? cnt : cnt - 1;
-        uint32_t j = 0;
-        for (; j + 2 <= upd; j += 2) {                                    // two steps per trip: rec offsets become immediates, half the loop control
-            seq_chain_step(tbl, recp + j * 4, win, wbase, st, Bc, bad);
-            seq_chain_step(tbl, recp + j * 4 + 4, win, wbase, st, Bc, bad);
-        }
-        if (j < upd) seq_chain_step(tbl, recp + j * 4, win, wbase, st, Bc, bad);
-        if (upd < cnt) {
-            const uint32_t e_ = tbl[st];
-            recp[upd * 4] = (uint16_t)st;
-            const uint32_t eb = SEQD_EBITS(e_);
-            const int32_t raw = (int32_t)(Bc - DUNI(eb + DPP_SHL(eb, 1) + DPP_SHL(eb, 2)));
-            bad |= (uint32_t)raw;
-            Bc = (uint32_t)(raw < 0 ? 0 : raw);
-        }
-        if (bad >> 31) ZB_FAIL();
-        __threadfence_block();
-        WAVE_SYNC();
-        ZLT(2);
-        // pass 2: every lane decodes the fields of its own sequence
+        uint32_t ll, ml, offBase;
+        if (!dec_seq_group(L, stream, g, cnt, nbSeq, lane, ll, ml, offBase)) ZB_FAIL();
         const bool valid = lane < cnt;
-        uint32_t ll = 0, ml = 0, offBase = 4;
-        {
-            uint32_t el = 0, eo = 0, em = 0, mine = 0;
-            if (valid) {
-                uint64_t r; __builtin_memcpy(&r, &L.rec[lane * 4], 8);
-                el = L.ll[(uint32_t)r & 0xFFFF]; em = L.ml[(uint32_t)(r >> 16) & 0xFFFF]; eo = L.of[(uint32_t)(r >> 32) & 0xFFFF];
-                mine = SEQD_TOT(el) + SEQD_TOT(eo) + SEQD_TOT(em);
-                if (g + lane + 1 == nbSeq) mine = SEQD_EBITS(el) + SEQD_EBITS(eo) + SEQD_EBITS(em);
-            }
-            uint32_t incl = mine;
-            for (uint32_t o = 1; o < LANES; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if (lane >= o) incl += v; }
-            if (valid) {
-                const uint32_t oc = SEQD_EBITS(eo), mbits = SEQD_EBITS(em), lbits = SEQD_EBITS(el);
-                const uint32_t lbase = L.cLLbase[SEQD_SYM(el)], mbase = L.cMLbase[SEQD_SYM(em)];
-                const uint32_t lo1 = Bgroup - (incl - mine) - oc;
-                offBase = (1u << oc) + ((uint32_t)(wld64(win, wbase, lo1 >> 3) >> (lo1 & 7)) & ((1u << oc) - 1));
-                const uint32_t lo2 = lo1 - mbits - lbits;
-                const uint32_t w2 = (uint32_t)(wld64(win, wbase, lo2 >> 3) >> (lo2 & 7));
-                ll = lbase + (w2 & ((1u << lbits) - 1));
-                ml = mbase + ((w2 >> lbits) & ((1u << mbits) - 1));
-            }
-        }
+        ZLT(1);
         if (__any(valid && offBase > 3 && offBase - 3 >= ZB_SYM)) ZB_FAIL();     // an offset of 2 GiB or more: not in a frame this form takes
-        ZLT(3);
         // pass 3: repeat offsets, on values that are either offsets or references into the incoming history
         uint32_t off = offBase - 3;
         {
@@ -552,7 +300,7 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
 #ifdef TSX_PROF2
     if (lane == 0 && zbprof) { unsigned long long* const zp = zbprof + ((size_t)chunk * ZB_MAX_BLOCKS + b) * 8; for (int k = 0; k < 6; k++) zp[k] = zlt_[k]; }
 #endif
-    if (Bc != 0) ZB_FAIL();                                             // every bit of the stream was used
+    if (stream.B != 0) ZB_FAIL();                                       // every bit of the stream was used
     if (lane == 0) { B->regen = litSize + sumML; B->endHist[0] = r0; B->endHist[1] = r1; B->endHist[2] = r2; B->ok = 1; }
 }
 
@@ -633,7 +381,7 @@ __global__ __launch_bounds__(ZB_SC_WAVES * LANES) void zb_scatter_kernel(const u
     if (btype == 1) { const uint32_t v = ZB_LIT | src[boff]; for (uint32_t i = tid; i < regen; i += ZB_SC_WAVES * LANES) words[myStart + i] = v; return; }
     const uint32_t litSize = DUNI(B->litSize), nbSeq = DUNI(B->nbSeq);
     const uint8_t* litPtr = litArena + DUNI(B->litAt);
-    if (DUNI(B->ltype) == 0) { const ZbLit h = zb_lit_header(src + boff, DUNI(B->bsize)); litPtr = src + boff + h.hl; }
+    if (DUNI(B->ltype) == 0) { const DecLit h = dec_lit_header(src + boff, DUNI(B->bsize)); litPtr = src + boff + h.hl; }
     const uint32_t* const sLL = seqArena + DUNI(B->seqAt); const uint32_t* const sML = sLL + seq_cap; const uint32_t* const sOF = sML + seq_cap;
     const uint32_t ngroups = (nbSeq + LANES - 1) / LANES;
     if (ngroups > ZB_SC_GROUPS) { if (tid == 0) ZB_STORE_AGENT(&C->mode, 0u); return; }   // (the decode kernel bounds the match lengths' sum: cannot happen)

@@ -1,6 +1,17 @@
 // Device-side pieces shared by the two frame-decoder kernels (zstd_dec.hip: one workgroup per chunk, blocks pipelined;
-// zstd_dec_blocks.hip: one workgroup per block, for small batches): format tables, bit readers, FSE / Huffman table builders,
-// the LDS state of a decoding workgroup and the copy helpers of the execution stage.  Included by those two files only.
+// zstd_dec_blocks.hip: one workgroup per block, for small batches).  Included by those two files only.  It holds:
+//   format tables, bit readers, the LDS state of a decoding workgroup (DecLds), FSE / Huffman table builders;
+//   every stage that parses frame bytes, once for both kernels:
+//     dec_frame_header    magic, descriptor, window, dictionary ID, content size
+//     dec_block_header    one block header; dec_frame_end: the checksum and the frame's end behind the last block
+//     dec_lit_header      literals-section header: raw / RLE / Huffman sizes and stream count
+//     dec_huf_streams     the 1 or 4 Huffman streams through per-stream LDS windows
+//     dec_seq_header      sequence count and table modes; dec_seq_table: one table from its description
+//     dec_seq_group       the sequence bit stream for one group of 64 sequences: end mark, window refill, initial states,
+//                         pass 1 (the state chain, seq_chain_step) and pass 2 (field extraction);
+//   the copy helpers of the chunk-serial form's execution stage.
+// What the forms do differently stays in their own files: repeat offsets (pass 3), execution, the state the chunk-serial form
+// carries across blocks, the block form's own limits, and what a failure means to each.
 #pragma once
 #include "zstd_common.h"
 
@@ -383,6 +394,326 @@ __device__ static void huf_buildX_wave(DecLds& L, uint32_t lane) {
         }
         L.hufX[x] = syms | (pos << 24) | (ns << 28);
     }
+}
+
+// ---- frame parsing, one helper per stage ----------------------------------------------------------------------------------
+// Both kernels parse frames through these, so a frame means the same to both: the block-parallel form may only take a chunk that
+// it decodes exactly as the chunk-serial form would.  The helpers report failure (a status, a false, an ok of 0); what a failure
+// does - an error code of the chunk-serial form, the chunk handed back by the block form - is the caller's business.
+
+// Frame header: magic, descriptor, window, dictionary ID, content size.  The checks run in this order, and the order decides
+// the code: a frame that declares no content size is TSX_E_BAD_SIZE, whatever follows its dictionary ID.  (The dst_cap check
+// is the caller's: TSX_E_DST_TOO_SMALL in the chunk-serial form, the chunk handed back in the block form.)
+struct DecFrame { int32_t status; uint32_t p; uint64_t contentSize; bool hasChecksum; };   // p: the first block header
+__device__ __forceinline__ static DecFrame dec_frame_header(const uint8_t* __restrict__ src, uint32_t srcSize) {
+    DecFrame f; f.status = DERR_FRAME; f.p = 0; f.contentSize = 0; f.hasChecksum = false;
+    if (srcSize < 6) return f;
+    if (src[0] != 0x28 || src[1] != 0xB5 || src[2] != 0x2F || src[3] != 0xFD) return f;
+    const uint32_t fhd = src[4];
+    const uint32_t single = (fhd >> 5) & 1, dictFlag = fhd & 3, fcsFlag = fhd >> 6;
+    f.hasChecksum = (fhd >> 2) & 1;
+    if (fhd & 8) return f;                                              // reserved bit
+    uint32_t p = 5;
+    if (!single) { if (p >= srcSize) return f; if ((src[p] >> 3) > 21) return f; p++; }
+    const uint32_t dl = dictFlag == 0 ? 0 : dictFlag == 1 ? 1 : dictFlag == 2 ? 2 : 4;
+    if (p + dl > srcSize) return f;
+    uint32_t dictId = 0; for (uint32_t i = 0; i < dl; i++) dictId |= (uint32_t)src[p + i] << (8 * i);
+    if (dictId) return f;                                               // dictionaries are not supported (the reference uses none)
+    p += dl;
+    const uint32_t fl = fcsFlag == 0 ? single : fcsFlag == 1 ? 2 : fcsFlag == 2 ? 4 : 8;
+    if (fl == 0) { f.status = TSX_E_BAD_SIZE; return f; }               // unknown content size: "Invalid decompressed size"
+    if (p + fl > srcSize) return f;
+    uint64_t contentSize = 0;
+    for (uint32_t i = 0; i < fl; i++) contentSize |= (uint64_t)src[p + i] << (8 * i);
+    if (fl == 2) contentSize += 256;
+    f.status = TSX_OK; f.p = p + fl; f.contentSize = contentSize;
+    return f;
+}
+
+// The block header at p.  ok = 0 on a reserved block type, a compressed block outside 2 .. Block_Maximum_Size bytes, or a body
+// that runs past the frame.  next = the position behind the body (a raw block's bsize bytes, an RLE block's one byte).
+struct DecBlockHdr { uint32_t ok, last, btype, bsize, off, next; };    // off: where the body starts
+__device__ __forceinline__ static DecBlockHdr dec_block_header(const uint8_t* __restrict__ src, uint32_t srcSize, uint32_t p) {
+    DecBlockHdr h; h.ok = 0; h.last = 0; h.btype = 0; h.bsize = 0; h.off = p; h.next = p;
+    if (p + 3 > srcSize) return h;
+    const uint32_t bh = (uint32_t)src[p] | ((uint32_t)src[p + 1] << 8) | ((uint32_t)src[p + 2] << 16);
+    h.off = p + 3; h.last = bh & 1; h.btype = (bh >> 1) & 3; h.bsize = bh >> 3;
+    if (h.btype == 3) return h;
+    if (h.btype == 2 && (h.bsize > ZS_BLOCK_MAX || h.bsize < 2)) return h;
+    const uint32_t body = h.btype == 1 ? 1 : h.bsize;
+    if (h.off + body > srcSize) return h;
+    h.next = h.off + body; h.ok = 1;
+    return h;
+}
+// Behind the last block: the optional content checksum (skipped, not verified), then the frame's end.
+__device__ __forceinline__ static bool dec_frame_end(uint32_t p, uint32_t srcSize, bool hasChecksum) {
+    if (hasChecksum) { if (p + 4 > srcSize) return false; p += 4; }
+    return p == srcSize;
+}
+
+// Literals-section header of a compressed block -> section size (0 = malformed).  hl = header bytes, csize = Huffman
+// section bytes (tree description + streams) behind them.
+struct DecLit { uint32_t ltype, hl, litSize, csize, streams, section; };
+__device__ __forceinline__ static DecLit dec_lit_header(const uint8_t* __restrict__ blk, uint32_t bsize) {
+    DecLit h; h.section = 0; h.csize = 0; h.streams = 1;
+    const uint32_t b0 = blk[0], sf = (b0 >> 2) & 3;
+    h.ltype = b0 & 3;
+    if (h.ltype < 2) {
+        if (sf == 0 || sf == 2) { h.litSize = b0 >> 3; h.hl = 1; }
+        else if (sf == 1) { if (bsize < 2) return h; h.litSize = (b0 >> 4) + ((uint32_t)blk[1] << 4); h.hl = 2; }
+        else { if (bsize < 3) return h; h.litSize = (b0 >> 4) + ((uint32_t)blk[1] << 4) + ((uint32_t)blk[2] << 12); h.hl = 3; }
+        if (h.litSize > ZS_BLOCK_MAX) return h;
+        const uint32_t sec = h.ltype == 0 ? h.hl + h.litSize : h.hl + 1;
+        if (sec > bsize) return h;
+        h.section = sec;
+    } else {
+        uint32_t bits;
+        if (sf == 0) { h.hl = 3; bits = 10; h.streams = 1; }
+        else if (sf == 1) { h.hl = 3; bits = 10; h.streams = 4; }
+        else if (sf == 2) { h.hl = 4; bits = 14; h.streams = 4; }
+        else { h.hl = 5; bits = 18; h.streams = 4; }
+        if (h.hl > bsize) return h;
+        uint64_t v = 0;
+        for (uint32_t i = 0; i < h.hl; i++) v |= (uint64_t)blk[i] << (8 * i);
+        h.litSize = (uint32_t)(v >> 4) & ((1u << bits) - 1);
+        h.csize = (uint32_t)(v >> (4 + bits)) & ((1u << bits) - 1);
+        if (h.litSize > ZS_BLOCK_MAX || h.hl + h.csize > bsize || h.litSize == 0) return h;
+        h.section = h.hl + h.csize;
+    }
+    return h;
+}
+
+// The 1 or 4 Huffman streams of a literals section (tree built: L.hufX, L.hufLog), on lanes 0-3: pay / payload = the section's
+// bytes behind the tree description.  Each stream decodes through its own LDS window of the stream, refilled by the whole wave
+// whenever a lane gets close to its window's lower edge (a reload from global memory would be a dependent round trip every four
+// symbols).  Returns false (wave-uniform) on a malformed stream.
+__device__ __forceinline__ static bool dec_huf_streams(DecLds& L, const uint8_t* __restrict__ pay, uint32_t payload, uint32_t streams, uint32_t litSize,
+                                                       uint8_t* __restrict__ lit, uint32_t lane) {
+    uint32_t sOff[5], sCnt[4];
+    if (streams == 1) { sOff[0] = 0; sOff[1] = payload; sOff[2] = sOff[3] = sOff[4] = payload; sCnt[0] = litSize; sCnt[1] = sCnt[2] = sCnt[3] = 0; }
+    else {
+        if (payload < 10) return false;
+        const uint32_t s1 = pay[0] | (pay[1] << 8), s2 = pay[2] | (pay[3] << 8), s3 = pay[4] | (pay[5] << 8);
+        if (6 + (uint64_t)s1 + s2 + s3 >= payload) return false;
+        sOff[0] = 6; sOff[1] = 6 + s1; sOff[2] = sOff[1] + s2; sOff[3] = sOff[2] + s3; sOff[4] = payload;
+        const uint32_t seg = (litSize + 3) / 4;
+        if (3 * seg > litSize) return false;
+        sCnt[0] = sCnt[1] = sCnt[2] = seg; sCnt[3] = litSize - 3 * seg;
+    }
+    bool ok = true;
+    const bool mine = lane < streams;
+    uint32_t o = 0; for (uint32_t k = 0; k < lane && k < 4; k++) o += mine ? sCnt[k] : 0;
+    const uint32_t cnt = mine ? sCnt[lane] : 0, sn = mine ? sOff[lane + 1] - sOff[lane] : 0, sbeg = mine ? sOff[lane] : 0;
+    uint8_t* const outp = lit + o;
+    // Bh = bits of the stream not read yet (cursor from the top; the last byte carries the end mark).  A step decodes four
+    // symbols (<= 44 bits) from ONE 8-byte window read at the cursor, no branches inside; the last symbols of a stream (fewer
+    // than four left, or fewer than 44 bits) go one at a time, with the bits below the stream's first one read as zeros like
+    // libzstd's container does.
+    uint32_t hi = 0, Bh = 0; bool hdone = !mine;
+    if (mine) {
+        const uint32_t lastByte = sn ? pay[sbeg + sn - 1] : 0;
+        if (lastByte == 0) { ok = false; hdone = true; }
+        else Bh = 8 * (sn - 1) + dhb32(lastByte);
+    }
+    const uint32_t tableLog = L.hufLog, tmask = (1u << tableLog) - 1;
+    for (;;) {
+        const uint32_t myTop = hdone ? 0 : (Bh >> 3) + 8;                                  // bytes past the stream's end are zeros
+        const uint32_t myWb = myTop > ZS_HWIN ? (myTop - ZS_HWIN + 15) & ~15u : 0;       // top - wb <= ZS_HWIN = one 16-byte piece per lane
+        for (uint32_t s_ = 0; s_ < streams; s_++) {
+            const uint32_t top = (uint32_t)__builtin_amdgcn_readlane(myTop, (int)s_), wb = (uint32_t)__builtin_amdgcn_readlane(myWb, (int)s_), beg = (uint32_t)__builtin_amdgcn_readlane(sbeg, (int)s_), n_ = (uint32_t)__builtin_amdgcn_readlane(sn, (int)s_);
+            const uint32_t k = lane * 16;
+            if (wb + k < top) {
+                uint4 v;
+                if (wb + k + 16 <= n_) __builtin_memcpy(&v, pay + beg + wb + k, 16);
+                else { uint8_t tmp[16]; for (uint32_t j = 0; j < 16; j++) tmp[j] = wb + k + j < n_ ? pay[beg + wb + k + j] : 0; __builtin_memcpy(&v, tmp, 16); }
+                *reinterpret_cast<uint4*>(&L.hwin[s_ * (ZS_HWIN + 16) + k]) = v;
+            }
+        }
+        __threadfence_block();
+        WAVE_SYNC();
+        if (!hdone) {
+            const uint8_t* const win = &L.hwin[lane * (ZS_HWIN + 16)];
+            // five table reads per 8-byte window read: each yields the one to three symbols coded in the next 11 bits
+            while (hi + 16 <= cnt && Bh >= 56 && ((Bh - 56) >> 3) >= myWb) {
+                const uint32_t lo = Bh - 56;
+                const uint64_t c = wld64(win, myWb, lo >> 3) >> (lo & 7);                 // bits [lo, lo + 56) of the stream
+                uint32_t used = 0;
+                #pragma unroll
+                for (int k = 0; k < 5; k++) {
+                    const uint32_t e = L.hufX[(uint32_t)(c >> (45 - used)) & 0x7FF];
+                    const uint32_t sy = e & 0xFFFFFF;                                    // one byte of slack behind the symbols
+                    __builtin_memcpy(outp + hi, &sy, 4);
+                    hi += e >> 28; used += (e >> 24) & 15;
+                }
+                Bh -= used;
+            }
+            while (hi < cnt && (hi + 16 > cnt || Bh < 56)) {                               // the stream's tail, one symbol at a time
+                const uint32_t need = Bh < tableLog ? Bh : tableLog, lo = Bh - need;
+                if ((lo >> 3) < myWb) break;                                               // behind the window: refill first
+                const uint32_t bits = (uint32_t)(wld64(win, myWb, lo >> 3) >> (lo & 7)) & ((1u << need) - 1);
+                const uint32_t e = huf_decode1(L, (bits << (tableLog - need)) & tmask, tableLog);
+                if ((e >> 8) > Bh) { ok = false; hdone = true; break; }                     // reads past the stream's first bit
+                outp[hi++] = (uint8_t)e; Bh -= e >> 8;
+            }
+            if (!hdone && hi >= cnt) { if (Bh != 0) ok = false; hdone = true; }             // every bit used, none missing
+        }
+        WAVE_SYNC();
+        if (__all(hdone)) break;
+    }
+    return !__any(!ok);
+}
+
+// Sequences-section header at q: the number of sequences and, when there are any, the Symbol_Compression_Modes byte.  ok = 0
+// when it runs past the block, declares more sequences than a block can hold, sets the reserved mode bits, or - with no
+// sequences - leaves bytes in the block.  t = the first table description.
+struct DecSeqHdr { uint32_t ok, nbSeq, modes, t; };
+__device__ __forceinline__ static DecSeqHdr dec_seq_header(const uint8_t* __restrict__ blk, uint32_t bsize, uint32_t q) {
+    DecSeqHdr h; h.ok = 0; h.nbSeq = 0; h.modes = 0; h.t = 0;
+    if (q >= bsize) return h;
+    uint32_t nbSeq = blk[q];
+    if (nbSeq < 128) q += 1;
+    else if (nbSeq < 255) { if (q + 2 > bsize) return h; nbSeq = ((nbSeq - 128) << 8) + blk[q + 1]; q += 2; }
+    else { if (q + 3 > bsize) return h; nbSeq = blk[q + 1] + ((uint32_t)blk[q + 2] << 8) + 0x7F00; q += 3; }
+    h.nbSeq = nbSeq;
+    if (nbSeq > ZS_BLOCK_MAX / 3 + 1) return h;                        // 128 KiB / minMatch 3 = 43691 at most in a valid block
+    if (nbSeq == 0) { h.ok = q == bsize; return h; }
+    if (q >= bsize) return h;
+    h.modes = blk[q]; h.t = q + 1;
+    h.ok = (h.modes & 3) == 0;
+    return h;
+}
+
+// One of the three sequence tables (k: 0 literal lengths, 1 offsets, 2 match lengths) from its description: mode 0 predefined,
+// 1 RLE, 2 FSE-compressed (a Repeat, mode 3, is the caller's).  Lane 0 parses the description (a short serial bit parse), the
+// whole wave builds the table (fse_buildSeqTable_wave).  desc / avail: the description's bytes.  Returns the bytes it used, -1
+// (wave-uniform) when the description is malformed.
+__device__ __forceinline__ static int32_t dec_seq_table(DecLds& L, int k, uint32_t mode, const uint8_t* __restrict__ desc, uint32_t avail, uint32_t lane) {
+    SeqD* const dt = k == 0 ? L.ll : k == 1 ? L.of : L.ml;
+    uint32_t* const logp = k == 0 ? &L.llLog : k == 1 ? &L.ofLog : &L.mlLog;
+    const uint32_t maxSymK = k == 0 ? 35 : k == 1 ? 31 : 52, maxLogK = k == 0 ? 9 : k == 1 ? 8 : 9;
+    if (mode == 0) {
+        const short* const dn = k == 0 ? dLLnorm : k == 1 ? dOFnorm : dMLnorm;
+        const uint32_t dmax = k == 0 ? 35 : k == 1 ? 28 : 52, dlog = k == 1 ? 5 : 6;
+        if (lane <= dmax) L.norm[lane] = dn[lane];
+        if (lane == 0) *logp = dlog;
+        __threadfence_block();
+        WAVE_SYNC();
+        return fse_buildSeqTable_wave(dt, L, dmax, dlog, k, lane) ? 0 : -1;
+    }
+    if (mode == 1) {                                                    // one symbol, no state bits
+        if (avail < 1) return -1;
+        const uint32_t sym = DUNI(desc[0]);
+        if (sym > maxSymK) return -1;
+        if (lane == 0) { dt[0] = SEQD(0, 0, seq_ebits(L, sym, k), sym); *logp = 0; }
+        __threadfence_block();
+        WAVE_SYNC();
+        return 1;
+    }
+    if (avail < 1) return -1;
+    if (lane == 0) {
+        uint32_t ms = maxSymK, tl = 0;
+        const uint32_t used = fse_readNCount(L.norm, &ms, &tl, desc, avail, maxLogK);
+        L.scal[0] = used; L.scal[3] = ms; L.scal[4] = tl;
+        if (used) *logp = tl;
+    }
+    __threadfence_block();
+    WAVE_SYNC();
+    const uint32_t used = DUNI(L.scal[0]), ms = DUNI(L.scal[3]), tl = DUNI(L.scal[4]);
+    WAVE_SYNC();
+    return used && fse_buildSeqTable_wave(dt, L, ms, tl, k, lane) ? (int32_t)used : -1;
+}
+
+// The sequence bit stream of a compressed block (bytes / n: behind the table descriptions, n >= 1) and where its decoding stands.
+struct DecSeqStream { const uint8_t* bytes; uint32_t n, B, wbase, st; };   // B: bits not read yet (the cursor, from the top); st: this lane's state
+// One group of up to 64 sequences, the first at index g of the block's nbSeq (cnt = min(64, nbSeq - g), wave-uniform): this
+// lane's sequence g + lane -> its literal length, match length and offset code (offBase: 1..3 repeat, else offset + 3).  The
+// tables are built (L.ll, L.of, L.ml and their logs, L.cLLbase / L.cMLbase, L.zeroEntry).  The first group also reads the end
+// mark and the initial states.  The stream is one serial chain (read backwards; each FSE state transition says how many bits
+// the next one reads), staged through an LDS window that the whole wave refills.  Only the part of a sequence that IS serial
+// runs serially: pass 1 walks the three state machines (seq_chain_step) and leaves each sequence's states in L.rec; pass 2 lets
+// every lane pull its sequence's extra bits out of the window - all 64 at once.  Returns false (wave-uniform) when the stream
+// is malformed or shorter than its sequences need; whether every bit was used is the caller's check, after the last group.
+__device__ __forceinline__ static bool dec_seq_group(DecLds& L, DecSeqStream& S, uint32_t g, uint32_t cnt, uint32_t nbSeq, uint32_t lane,
+                                                     uint32_t& ll, uint32_t& ml, uint32_t& offBase) {
+    const uint8_t* const win = L.swin + ZS_DPAD;
+    if (g == 0) {                                                       // BIT_initDStream: the last byte carries the end mark
+        const uint32_t lastByte = DUNI(S.bytes[S.n - 1]);
+        if (lastByte == 0) return false;
+        S.B = 8 * (S.n - 1) + dhb32(lastByte);
+    }
+    // 64 sequences read at most 64 * 89 bits = 712 bytes below the cursor; every read is an 8-byte load at byte (bit >> 3), so
+    // the window holds [wbase, (B >> 3) + 8) with the bytes past the stream's end as zeros
+    if (g == 0 || (S.wbase != 0 && (S.B >> 3) < S.wbase + 736)) {
+        WAVE_SYNC();                                                    // everyone is done with the previous window
+        const uint32_t top = (S.B >> 3) + 8;
+        S.wbase = top > ZS_DWIN ? (top - ZS_DWIN) & ~15u : 0;
+        for (uint32_t k = lane * 16; S.wbase + k < top; k += LANES * 16) {
+            uint4 v;
+            if (S.wbase + k + 16 <= S.n) __builtin_memcpy(&v, S.bytes + S.wbase + k, 16);
+            else { uint8_t tmp[16]; for (uint32_t j = 0; j < 16; j++) tmp[j] = S.wbase + k + j < S.n ? S.bytes[S.wbase + k + j] : 0; __builtin_memcpy(&v, tmp, 16); }
+            *reinterpret_cast<uint4*>(&L.swin[ZS_DPAD + k]) = v;
+        }
+        if (lane < ZS_DPAD / 4) reinterpret_cast<uint32_t*>(L.swin)[lane] = 0;      // the margin in front of the window
+        __threadfence_block();
+        WAVE_SYNC();
+        if (g == 0) {                                                   // initial states: LL, OF, ML (ZSTD_initFseState order)
+            const uint32_t llLog = DUNI(L.llLog), ofLog = DUNI(L.ofLog), mlLog = DUNI(L.mlLog);
+            const uint32_t lo = S.B - (llLog + ofLog + mlLog);          // <= 26 bits
+            if ((int32_t)lo < 0) return false;
+            const uint32_t w = DUNI((uint32_t)(wld64(win, S.wbase, lo >> 3) >> (lo & 7)));
+            const uint32_t sm = w & ((1u << mlLog) - 1), so = (w >> mlLog) & ((1u << ofLog) - 1), sl = (w >> (mlLog + ofLog)) & ((1u << llLog) - 1);
+            S.st = lane == 0 ? sl : lane == 1 ? sm : lane == 2 ? so : 0;
+            S.B = lo;
+        }
+    }
+    // pass 1: the chain, on the vector unit (seq_chain_step).  An over-read shows as a negative cursor (collected in `bad`,
+    // checked once per group).  The last sequence of a block reads no update bits: peeled off the loop.
+    const SeqD* const tbl = lane == 0 ? L.ll : lane == 1 ? L.ml : lane == 2 ? L.of : &L.zeroEntry;   // lanes 3..63 carry state 0
+    uint16_t* const recp = &L.rec[lane < 3 ? lane : 3];
+    uint32_t bad = 0;
+    const uint32_t Bgroup = S.B;
+    const uint32_t upd = g + cnt < nbSeq ? cnt : cnt - 1;
+    uint32_t j = 0;
+    for (; j + 2 <= upd; j += 2) {                                      // two steps per trip: rec offsets become immediates, half the loop control
+        seq_chain_step(tbl, recp + j * 4, win, S.wbase, S.st, S.B, bad);
+        seq_chain_step(tbl, recp + j * 4 + 4, win, S.wbase, S.st, S.B, bad);
+    }
+    if (j < upd) seq_chain_step(tbl, recp + j * 4, win, S.wbase, S.st, S.B, bad);
+    if (upd < cnt) {
+        const uint32_t e_ = tbl[S.st];
+        recp[upd * 4] = (uint16_t)S.st;
+        const uint32_t eb = SEQD_EBITS(e_);
+        const int32_t raw = (int32_t)(S.B - DUNI(eb + DPP_SHL(eb, 1) + DPP_SHL(eb, 2)));
+        bad |= (uint32_t)raw;
+        S.B = (uint32_t)(raw < 0 ? 0 : raw);
+    }
+    if (bad >> 31) return false;                                        // the stream is shorter than its sequences need
+    __threadfence_block();
+    WAVE_SYNC();
+    // pass 2: every lane decodes the fields of its own sequence from the window; its cursor is the group's minus the bits of the
+    // sequences before it (prefix sum)
+    const bool valid = lane < cnt;
+    ll = 0; ml = 0; offBase = 4;
+    uint32_t el = 0, eo = 0, em = 0, mine = 0;
+    if (valid) {
+        uint64_t r; __builtin_memcpy(&r, &L.rec[lane * 4], 8);
+        el = L.ll[(uint32_t)r & 0xFFFF]; em = L.ml[(uint32_t)(r >> 16) & 0xFFFF]; eo = L.of[(uint32_t)(r >> 32) & 0xFFFF];
+        mine = SEQD_TOT(el) + SEQD_TOT(eo) + SEQD_TOT(em);
+        if (g + lane + 1 == nbSeq) mine = SEQD_EBITS(el) + SEQD_EBITS(eo) + SEQD_EBITS(em);
+    }
+    uint32_t incl = mine;
+    for (uint32_t o = 1; o < LANES; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+    if (valid) {
+        const uint32_t oc = SEQD_EBITS(eo), mbits = SEQD_EBITS(em), lbits = SEQD_EBITS(el);
+        const uint32_t lbase = L.cLLbase[SEQD_SYM(el)], mbase = L.cMLbase[SEQD_SYM(em)];
+        const uint32_t lo1 = Bgroup - (incl - mine) - oc;               // offset bits first (<= 31), then ML, then LL (<= 16 each)
+        offBase = (1u << oc) + ((uint32_t)(wld64(win, S.wbase, lo1 >> 3) >> (lo1 & 7)) & ((1u << oc) - 1));
+        const uint32_t lo2 = lo1 - mbits - lbits;
+        const uint32_t w2 = (uint32_t)(wld64(win, S.wbase, lo2 >> 3) >> (lo2 & 7));
+        ll = lbase + (w2 & ((1u << lbits) - 1));
+        ml = mbase + ((w2 >> lbits) & ((1u << mbits) - 1));
+    }
+    return true;
 }
 
 // Per-lane copy of a short, non-overlapping run (a literal run, or a match whose source is already final): up to four

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Phase laps of zb_decode_kernel (block-parallel decoder form) for a few Kafka-like chunks: libtsxform_prof2.so (`make -C csrc prof2`),
-clock64() laps per (chunk, block).  Sequence wave: 0 tables, 1 window refills, 2 chain (pass 1), 3 fields (pass 2), 4 repeat offsets
-(pass 3), 5 stores + sums; literal wave: 6 tree + table, 7 streams.  Prints the mean per block and the share of the wave's total."""
+clock64() laps per (chunk, block).  Sequence wave: 0 tables, 1 bit stream (window refills, chain and fields: passes 1 and 2, one
+shared helper), 4 repeat offsets (pass 3), 5 stores + sums (2 and 3 are unused); literal wave: 6 tree + table, 7 streams.  Prints the mean
+per block and the share of the wave's total."""
 import ctypes as C
 import os
 import sys
@@ -48,10 +49,12 @@ assert (e["status"] == 0).all() and torch.equal(back, src)
 p = prof.cpu().numpy().reshape(n, ZB_MAX_BLOCKS, 8)
 used = p[:, :, :6].sum(axis=2) > 0
 m = p[used].mean(axis=0)
-names = ["seq: tables", "seq: window refills", "seq: chain (pass 1)", "seq: fields (pass 2)", "seq: repeat offsets (pass 3)", "seq: stores + sums",
+names = ["seq: tables", "seq: bit stream (passes 1-2)", None, None, "seq: repeat offsets (pass 3)", "seq: stores + sums",
          "lit: tree + table", "lit: streams"]
 seq_tot, lit_tot = m[:6].sum(), m[6:].sum()
 print("blocks with sequences: %d of %d chunks; ctx timing unzstd %.3f ms" % (used.sum(), n, N.ctx_timing(ctx).unzstd_ms))
 for k in range(8):
+    if names[k] is None:
+        continue
     print("  %-32s %12.0f ticks  (%5.1f %% of its wave)" % (names[k], m[k], 100.0 * m[k] / (seq_tot if k < 6 else lit_tot)))
 print("  sequence wave total %.0f ticks, literal wave total %.0f ticks" % (seq_tot, lit_tot))
