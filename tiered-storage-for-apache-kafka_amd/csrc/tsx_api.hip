@@ -1,10 +1,8 @@
-// C-ABI front end of libtsxform: device/context management, the compressor service's host side and the batch pipelines.
+// C-ABI front end of libtsxform: device/context management and the batch pipelines (the compressor service's host side: tsx_service.hip).
 // See include/tsxform.h for the contract and the reference call sites each entry point replaces.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <deque>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -14,49 +12,17 @@
 #include <string.h>
 #include <vector>
 
-#include "tsx_internal.h"
-#include "zstd_gpu.h"
+#include "tsx_host.h"
+#include "tsx_service.h"
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { tsx_set_err(#x, e_); return TSX_E_DEVICE; } } while (0)
-
-// ---- configuration -----------------------------------------------------------------------------------------------------------------
-// Read ONCE, in tsx_init: tsx_init_ex's tsx_config first, then the environment of the process for the few settings a deployment may
-// want to change without touching code (INTEGRATION.md 5 lists them).  No entry point on a data path reads the environment.  The
-// fields under "test hooks" have no environment variable: tests and measurement tools set them through tsx_debug_config().
-struct tsx_cfg {
-    uint32_t reserved_cus = 0xFFFFFFFFu;  // compute units the compressor service leaves to everything else (0xFFFFFFFF: one per shader engine); TSX_FETCH_RESERVED_CUS
-    uint32_t svc_max_launch_ms = 60000;   // age limit of one launch of the service kernel (0 = none); TSX_SERVICE_MAX_LAUNCH_MS
-    uint32_t svc_idle_exit_us = 2000;     // the service kernel ends when it has had nothing to do for this long (callers in a closed loop need ~1 ms to come back)
-    uint32_t fetch_quiet_ms = 2000;       // tsx_config.fetch_quiet_ms: the reserved CUs work for the compressor too (guest waves) once no fetch has been seen for this long; 0 = never; TSX_FETCH_QUIET_MS
-    uint32_t svc_keep_waves = 0;          // tsx_config.fetch_shared_cu_waves: compressor waves that stay on a reserved CU all the same; TSX_FETCH_SHARED_CU_WAVES
-    long long pool_idle_bytes = -1;       // idle pooled workspace kept per device (-1: 4/9 of its memory); TSX_POOL_IDLE_BYTES
-    uint32_t zstd_sched = 0;              // parser speculation schedule k0 | k1 << 8 (0 = the kernel's default; same bytes); TSX_ZSTD_SCHED
-    bool debug = false;                   // TSX_DEBUG: HIP failures go to stderr as they happen
-    bool allow_any_arch = false;          // TSX_ALLOW_ANY_ARCH: the CPU test harness
-    // ---- test hooks (tsx_debug_config) ----
-    uint32_t dec_block_chunks = 256;      // largest detransform batch that takes the block-parallel decoder form (0 = never)
-    uint32_t comp_pieces = 4;             // members a compressing host-memory batch is cut into (input copy of piece k + 1 overlaps piece k's waves)
-    long long sub_bytes = 0;              // input bytes per piece of the staging pipeline (0 = TSX_SUB_BYTES)
-    bool stages_separate = false;         // one launch per stage instead of the whole chain in the compressor wave
-    bool no_pipeline = false;             // host-memory batches in one piece
-    bool no_zero_copy_out = false;        // never let the waves write into the caller's buffer
-    bool zero_copy_packed = false;        // explicit contexts: packed output in place too
-    bool gcm_setup_kernel = false;        // key schedule by gcm_setup_kernel instead of on the host
-    bool no_dec_pieces = false;           // block-form fetches in one piece
-    uint32_t svc_waves_per_cu = 0;        // workgroups of a service launch per CU (0 = what the runtime says is resident at once; measurements only)
-    bool svc_normal_priority = false;     // the service's stream like any other (default: the device's LOWEST stream priority, a hardware queue of its own pool)
-    bool trace = false;                   // timestamps of a batch's phases on stderr (tools/fetch_block_probe.py)
-    uint32_t svc_idle_nap_max = 0;        // measurements: tsx_svc_launch.idle_nap_max
-    bool svc_no_spread = false;           // measurements: tickets to whoever asks first (no spreading of a partial load over the CUs)
-    uint32_t svc_guest_looks = 3;         // measurements: which looks at the yield word guest waves make (1: before every block, 2: while idle)
-};
-static tsx_cfg g_cfg;
+tsx_cfg g_cfg;
 
 static thread_local char g_last_err[256];
-static void tsx_set_err(const char* what, hipError_t e) {
+void tsx_set_err(const char* what, hipError_t e) {
     snprintf(g_last_err, sizeof g_last_err, "%s failed: %s", what, hipGetErrorString(e));
     if (g_cfg.debug) fprintf(stderr, "[tsxform] %s\n", g_last_err);
 }
+void tsx_set_errmsg(const char* text) { snprintf(g_last_err, sizeof g_last_err, "%s", text); }
 
 static void cfg_from_env(tsx_cfg& c) {
     if (const char* e = getenv("TSX_FETCH_RESERVED_CUS")) { const long v = atol(e); c.reserved_cus = (uint32_t)(v < 0 ? 0 : v > 128 ? 128 : v); }
@@ -77,88 +43,12 @@ extern "C" long long tsx_debug_config(const char* key, long long value) {
     CFG_FIELD(reserved_cus, uint32_t) CFG_FIELD(svc_max_launch_ms, uint32_t) CFG_FIELD(svc_idle_exit_us, uint32_t) CFG_FIELD(pool_idle_bytes, long long)
     CFG_FIELD(zstd_sched, uint32_t) CFG_FIELD(dec_block_chunks, uint32_t) CFG_FIELD(comp_pieces, uint32_t) CFG_FIELD(sub_bytes, long long)
     CFG_FIELD(stages_separate, bool) CFG_FIELD(no_pipeline, bool) CFG_FIELD(no_zero_copy_out, bool) CFG_FIELD(zero_copy_packed, bool)
-    CFG_FIELD(gcm_setup_kernel, bool) CFG_FIELD(no_dec_pieces, bool) CFG_FIELD(debug, bool) CFG_FIELD(svc_normal_priority, bool) CFG_FIELD(svc_waves_per_cu, uint32_t) CFG_FIELD(svc_keep_waves, uint32_t) CFG_FIELD(fetch_quiet_ms, uint32_t) CFG_FIELD(trace, bool) CFG_FIELD(svc_guest_looks, uint32_t) CFG_FIELD(svc_no_spread, bool) CFG_FIELD(svc_idle_nap_max, uint32_t)
+    CFG_FIELD(gcm_setup_kernel, bool) CFG_FIELD(no_dec_pieces, bool) CFG_FIELD(debug, bool) CFG_FIELD(svc_normal_priority, bool) CFG_FIELD(svc_keep_waves, uint32_t) CFG_FIELD(fetch_quiet_ms, uint32_t) CFG_FIELD(trace, bool)
 #undef CFG_FIELD
     return TSX_E_INVAL;
 }
 
-// Every entry point that selects a device puts the calling thread's current device back on the way out: the caller may share
-// the thread with another HIP user (a torch process, another JNI library) whose notion of "current device" is not ours to change.
-struct tsx_device_scope {
-    int prev = -1;
-    tsx_device_scope() { if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipGetLastError(); } }
-    ~tsx_device_scope() { if (prev >= 0) (void)hipSetDevice(prev); }
-    tsx_device_scope(const tsx_device_scope&) = delete;
-    tsx_device_scope& operator=(const tsx_device_scope&) = delete;
-};
-
-struct tsx_ctx;
 struct tsx_run;
-struct tsx_device;
-
-// ---- the compressor service, host side (device side: zstd_enc.hip, zstd_service_kernel; layout: tsx_internal.h) -----------------------
-// Rounds 2-4 launched one compressor kernel per batch (or per group of callers: the "launch combiner") and let the hardware's
-// dispatcher hand workgroups to freed wave slots.  Two things followed from a launch being the unit of work: the chip ran in
-// generations (a batch's stragglers held its hardware queue while slots sat empty; 18.0 GiB/s in a timed region against 18.7-20.4
-// continuously fed), and everything that is not a compressor wave starved - a freed 6.7 KB slot is refilled by the dispatcher before a
-// decoder workgroup finds three neighbouring ones: a fetch under upload load took 1-65 s (profiles/r04_mixed_load.txt).  Now a
-// compressing batch is a MEMBER of its device's queue: tickets in pinned memory, persistent waves that pull them, per-member completion
-// flags.  One kernel, on one stream that carries nothing else; it is (re)started by whoever publishes work and finds it gone, and by
-// the waiting callers' watchdog (a launch that ended - idle, age limit, every wave on a reserved CU - with tickets still unserved).
-struct tsx_svc_member { uint64_t id; uint32_t first, n; uint16_t slot; bool done; const uint32_t* h_flag; };
-struct tsx_service {
-    std::mutex mu; std::condition_variable cv;
-    tsx_svc_host* h = nullptr; tsx_svc_host* hd = nullptr;          // the queue in pinned host memory: host view, device alias
-    tsx_svc_dev* d = nullptr;
-    uint32_t* h_zero = nullptr;                                      // pinned zero word (resets of device words travel as copies, not kernels)
-    hipStream_t st = nullptr;                                        // the service kernel's stream: launches only - no events, no copies while it runs
-    uint32_t launch_id = 0;                                          // id of the last launch made
-    bool launched = false;                                           // a launch is out whose end this side has not seen yet
-    bool stop_dirty = false;                                         // the device's stop word must be cleared in front of the next launch
-    uint32_t paused = 0;                                             // > 0: no launches (memory management in progress)
-    uint32_t grid = 0, cu_keys = 0, cus = 0, cus_reserved = 0, waves_per_cu = 0, resident = 0, engines = 0;
-    uint32_t published = 0;
-    uint64_t next_id = 1;
-    std::deque<tsx_svc_member> out;                                  // members published and not yet retired, oldest first
-    std::vector<uint16_t> free_slots; uint16_t slot_gen[TSX_SVC_MEMBERS] = {0};
-    uint64_t launches = 0, watchdog_launches = 0, members = 0, chunks = 0, rotations = 0; double kernel_ms = 0;
-    bool rotating = false;                                           // a waiting fetch has asked the running launch to end (svc_rotate)
-    // The reservation follows the traffic.  "Foreground" = every batch that runs ordinary kernels (fetches above all): while one is in flight,
-    // and for fetch_quiet_ms after the last one, tsx_svc_host.yield is raised - guest waves on the reserved CUs hand their chunks back and
-    // leave (<= one block of their chunk later, ~30 ms), launches made meanwhile leave the reserved CUs alone.  A device that only uploads
-    // compresses on every CU.
-    std::atomic<uint32_t> fg_inflight{0};
-    std::atomic<int64_t> fg_last_ns{INT64_MIN / 2};                  // steady clock at the end of the last foreground batch
-    uint64_t guest_launches = 0, readmissions = 0;
-    // Guests come in launches of their own, next to the launch they help (tsx_svc_launch.guest_launch): on a second stream of the lowest priority
-    hipStream_t st_g = nullptr;
-    uint32_t g_launch_id = 0; bool g_launched = false; int64_t g_last_ns = INT64_MIN / 2;
-    int64_t launch_ns = 0;                                           // steady clock at the last launch of the service kernel itself
-    std::vector<void*> deferred_dev, deferred_host;                  // frees that wait for the kernel to be gone (svc_free_*)
-};
-
-struct tsx_device {
-    int hip_id = -1;
-    tsx_crc_tables* d_crc = nullptr;
-    tsx_aes_tables* d_aes = nullptr;
-    tsx_zstd_consts* d_zc = nullptr;
-    uint8_t* h_zeros = nullptr;                    // pinned sizeof(tsx_gcm_key) zero bytes: key material is wiped by COPYING zeros - a memset is a
-                                                   // kernel, and a kernel waits for a slot on a chip full of compressor waves (measured: 52 ms on
-                                                   // average, up to 489 ms, per wipe: profiles/r03_bench_rocprofv3_kernel_stats_before_zero_copy_wipes.csv)
-    char name[256] = {0};
-    char arch[256] = {0};
-    // pooled contexts of the ctx-less calls: idle ones, how many are out, batches served (all under g_mu)
-    std::vector<tsx_ctx*> idle;
-    size_t idle_bytes = 0;
-    size_t idle_cap = 0;                                     // most idle workspace kept (init_devices: a fraction of THIS device's memory)
-    std::vector<std::pair<void*, size_t>> spare_bwork;       // block-form decoder workspaces that left their context (pool_release), for the next one
-    std::unique_ptr<tsx_service> svc;
-    // copy streams of the context-less compressing calls, shared by the callers: ONE of each.  With a stream per caller a segment's copies
-    // stood behind other callers' in the engines' queues anyway, and more streams measured worse (profiles/r04_broker_shape_experiments.txt).
-    hipStream_t copy_in = nullptr, copy_out = nullptr;
-    uint32_t in_use = 0;
-    uint64_t batches = 0;
-};
 
 #define TSX_MAX_SUBS 64                 /* sub-batches of one host-memory batch (staging pipeline) */
 #define TSX_SUB_BYTES ((size_t)64 << 20) /* input bytes per sub-batch: >= 1000 workgroups of the GCM / CRC kernels */
@@ -223,6 +113,11 @@ static std::atomic<const char*> g_version{kUninitVersion};
 static std::mutex g_reg_mu;
 static std::vector<std::pair<uintptr_t, size_t>> g_registered;
 
+tsx_device* tsx_device_at(int index) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return index < 0 || index >= (int)g_devs.size() ? nullptr : &g_devs[index];
+}
+
 extern "C" uint32_t tsx_abi_version(void) { return TSX_ABI_VERSION; }
 
 // The string is composed in a buffer no reader can see yet and published with one pointer store at the end of a successful
@@ -245,331 +140,7 @@ extern "C" const char* tsx_strerror(int code) {
     }
 }
 
-// ---- service: whose turn the reserved CUs are ----------------------------------------------------------------------------------------
-static int64_t steady_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-// A batch of ordinary kernels begins / is over (no lock: this is the fetch path).  The counter first, the word second - svc_launch_locked
-// clears the word first and looks at the counter second, so one of the two always sees the other.
-static void svc_foreground_begin(tsx_device* dev) {
-    if (!dev->svc) return;
-    dev->svc->fg_inflight.fetch_add(1, std::memory_order_seq_cst);
-    __atomic_store_n(&dev->svc->h->yield, 1u, __ATOMIC_SEQ_CST);
-}
-// traffic = false: something that only needed room while it ran (a new context's first small copies, a helper copy) - it does not count as
-// a fetch having been seen: the next member published finds the device quiet and asks the launch, whose guests have left, to make way for one
-// that uses every CU again (svc_submit, readmission)
-static void svc_foreground_end(tsx_device* dev, bool traffic = true) {
-    if (!dev->svc) return;
-    if (traffic) dev->svc->fg_last_ns.store(steady_ns(), std::memory_order_seq_cst);
-    dev->svc->fg_inflight.fetch_sub(1, std::memory_order_seq_cst);
-}
-static bool svc_quiet(const tsx_service& s) {
-    return g_cfg.fetch_quiet_ms != 0 && s.fg_inflight.load(std::memory_order_seq_cst) == 0 &&
-           steady_ns() - s.fg_last_ns.load(std::memory_order_seq_cst) > (int64_t)g_cfg.fetch_quiet_ms * 1000000;
-}
-
-// A member is about to be published (mu held): the yield word follows the device's quietness - down when no fetch has been seen for fetch_quiet_ms
-// (word first, counter second: svc_foreground_begin does it the other way round, one of the two sees the other), up otherwise.  Guests read it, and
-// so does a wave of the launch itself that the hardware's scheduler has restored onto a reserved CU: on a quiet device it finishes its chunk there.
-static void svc_note_quiet_locked(tsx_service& s) {
-    if (!s.cus_reserved) return;
-    if (svc_quiet(s)) {
-        if (__atomic_load_n(&s.h->yield, __ATOMIC_SEQ_CST) == 0u) return;
-        __atomic_store_n(&s.h->yield, 0u, __ATOMIC_SEQ_CST);
-        if (s.fg_inflight.load(std::memory_order_seq_cst) != 0) __atomic_store_n(&s.h->yield, 1u, __ATOMIC_SEQ_CST);
-    } else if (__atomic_load_n(&s.h->yield, __ATOMIC_SEQ_CST) == 0u) __atomic_store_n(&s.h->yield, 1u, __ATOMIC_SEQ_CST);      // (fetch_quiet_ms was changed under a lowered word)
-}
-
-// ---- service: lifetime ------------------------------------------------------------------------------------------------------------------
-// Is the service kernel of this device still out?  (mu held.)  When its end is seen for the first time, its duration joins the statistics
-// and what waited for it to be gone is freed: hipFree / hipHostFree wait for EVERY stream of the device, i.e. for a kernel that lives
-// as long as uploads go on - nothing in this library frees device or pinned memory while that kernel may be running (svc_free_*).
-static bool svc_guests_running_locked(tsx_service& s) {
-    if (!s.g_launched) return false;
-    if (__atomic_load_n(&s.h->g_ended_launch, __ATOMIC_ACQUIRE) != s.g_launch_id) return true;
-    s.g_launched = false;
-    return false;
-}
-static void svc_collect_locked(tsx_service& s) {                         // (nothing of the service is alive: what waited for that is freed)
-    if (s.launched || s.g_launched) return;
-    for (void* p : s.deferred_dev) (void)hipFree(p);
-    for (void* p : s.deferred_host) (void)hipHostFree(p);
-    s.deferred_dev.clear(); s.deferred_host.clear();
-}
-static bool svc_running_locked(tsx_service& s) {
-    if (!s.launched) return false;
-    // the launch's last wave says so itself (tsx_svc_host.ended_launch): nothing is queued behind the kernel that could be asked
-    if (__atomic_load_n(&s.h->ended_launch, __ATOMIC_ACQUIRE) != s.launch_id) return true;
-    s.kernel_ms += (double)(s.h->t_last - s.h->t_first) / 1e5;           // 100 MHz ticks
-    s.launched = false;
-    // a rotation is over with the launch it asked to end - also when a pause overlapped that end (the flag must not survive into the next
-    // launch: svc_rotate would stay switched off for its whole life); only the host's stop word stays up while paused
-    if (s.rotating) { s.rotating = false; if (!s.paused) __atomic_store_n(&s.h->stop, 0u, __ATOMIC_RELEASE); }   // (the device's copy of the word is cleared in front of the next launch)
-    (void)svc_guests_running_locked(s);
-    svc_collect_locked(s);
-    return false;
-}
-// Is ANY kernel of the service still out - the launch or its guests?  (What must not free memory, or must wait for the device to be the caller's alone, asks this.)
-static bool svc_alive_locked(tsx_service& s) {
-    const bool a = svc_running_locked(s), g = svc_guests_running_locked(s);
-    if (!a && !g) svc_collect_locked(s);
-    return a || g;
-}
-
-// Start the service kernel (mu held, kernel known to be gone, device current).
-static int svc_launch_locked(tsx_service& s) {
-    if (s.paused) return TSX_OK;                                        // whoever paused the service starts it again (svc_resume)
-    if (s.stop_dirty) {
-        HIPCHK(hipMemcpyAsync(&s.d->stop, s.h_zero, 4, hipMemcpyHostToDevice, s.st));
-        s.stop_dirty = false;
-    }
-    tsx_svc_launch a{};
-    a.sched = g_cfg.zstd_sched;
-#ifdef HIPEMU
-    a.poll_ticks = 0; a.idle_exit_ticks = 0;                             // blocks run one after the other: nobody to wait for
-#else
-    a.poll_ticks = 500;                                                  // one look at the host's word per 5 us, device-wide
-    a.idle_exit_ticks = g_cfg.svc_idle_exit_us * 100u;
-#endif
-    const uint64_t age = (uint64_t)g_cfg.svc_max_launch_ms * 100000ull;
-    a.max_age_ticks_lo = (uint32_t)age; a.max_age_ticks_hi = (uint32_t)(age >> 32);
-    a.keep_waves = g_cfg.svc_keep_waves;
-    a.idle_nap_max = g_cfg.svc_idle_nap_max;
-#ifdef HIPEMU
-    a.guest_idle_ticks = 0;
-#else
-    a.guest_idle_ticks = 1000000;                                        // 10 ms
-#endif
-    a.spread_cus = g_cfg.svc_no_spread ? 0u : (s.cus > s.cus_reserved ? s.cus - s.cus_reserved : s.cus);
-#ifdef HIPEMU
-    // (the CPU harness runs one kernel at a time, its blocks one after the other: guests are part of the launch there, which is how its tests reach
-    //  the guests' code; on the device they come in launches of their own - svc_try_guests_locked)
-    if (s.cus_reserved && svc_quiet(s)) {
-        __atomic_store_n(&s.h->yield, 0u, __ATOMIC_SEQ_CST);             // word first, counter second (svc_foreground_begin)
-        if (s.fg_inflight.load(std::memory_order_seq_cst) != 0) __atomic_store_n(&s.h->yield, 1u, __ATOMIC_SEQ_CST);
-        else a.guests = 1u | (g_cfg.svc_guest_looks << 1);               // (bit 1: guests look at the yield word before every block, bit 2: and while idle)
-    }
-#endif
-    (void)hipGetLastError();
-    a.launch_id = s.launch_id + 1;
-    tsx_launch_zstd_service(s.st, s.hd, s.d, s.grid, a);
-    if (hipGetLastError() != hipSuccess) { snprintf(g_last_err, sizeof g_last_err, "launch of the compressor service kernel failed"); return TSX_E_DEVICE; }
-    s.launch_id = a.launch_id;
-    s.launched = true; s.launches++; s.guest_launches += a.guests ? 1u : 0u;
-    s.launch_ns = steady_ns();
-    return TSX_OK;
-}
-
-// Guests (mu held, device current): a launch of as many one-wave workgroups as the reserved CUs hold, made when the running launch has more chunks
-// queued than waves, no fetch has been seen for fetch_quiet_ms and no guests are out.  With every other slot of the chip taken the workgroups land
-// on the reserved CUs; one that lands elsewhere (the main launch is still arriving, or the chip is not full after all) leaves at once, and so does
-// every guest that finds the queue dry for ten milliseconds (callers that resubmit as soon as their batches complete leave the queue dry for 2 - 3 ms between
-// two rounds: the guests stay through that) - so guests are there exactly while the chip is full AND busy, the one regime in which a
-// chip without a free slot works well (profiles/r06_full_chip_with_idle_waves.txt).  The next fetch raises the yield word: they hand their chunks
-// back and leave (tsx_svc_host.yield).
-static void svc_try_guests_locked(tsx_service& s) {
-#ifndef HIPEMU
-    if (!s.cus_reserved || !g_cfg.fetch_quiet_ms || s.paused || s.rotating || !s.launched || !s.st_g) return;
-    if (svc_guests_running_locked(s) || !svc_quiet(s)) return;
-    const int64_t now = steady_ns();
-    if (now - s.g_last_ns < 20000000) return;                            // (a launch whose workgroups all left at once is tried again 20 ms later)
-    // not before the launch they are to help has arrived: its workgroups take a moment to be placed (~0.5 ms on a cold chip), and a guest that finds a
-    // free slot anywhere but on a reserved CU takes it - and leaves (measured: guests launched 1 ms behind their launch, 41 of 768 stayed)
-    if (now - s.launch_ns < 3000000) return;
-    uint64_t outstanding = 0;
-    for (const auto& m : s.out) if (!m.done && !__atomic_load_n(m.h_flag, __ATOMIC_ACQUIRE)) outstanding += m.n;
-    const uint32_t gwaves = s.cus_reserved * s.waves_per_cu;
-    if (outstanding <= (uint64_t)(s.grid > gwaves ? s.grid - gwaves : s.grid)) return;     // every queued chunk has a wave of the launch itself
-    s.g_last_ns = now;
-    __atomic_store_n(&s.h->yield, 0u, __ATOMIC_SEQ_CST);                 // word first, counter second (svc_foreground_begin)
-    if (s.fg_inflight.load(std::memory_order_seq_cst) != 0) { __atomic_store_n(&s.h->yield, 1u, __ATOMIC_SEQ_CST); return; }
-    tsx_svc_launch a{};
-    a.sched = g_cfg.zstd_sched; a.poll_ticks = 500; a.idle_exit_ticks = g_cfg.svc_idle_exit_us * 100u;
-    const uint64_t age = (uint64_t)g_cfg.svc_max_launch_ms * 100000ull;
-    a.max_age_ticks_lo = (uint32_t)age; a.max_age_ticks_hi = (uint32_t)(age >> 32);
-    a.guest_idle_ticks = 1000000; a.guest_launch = 1; a.guests = 1u | (g_cfg.svc_guest_looks << 1);
-    a.spread_cus = 0;                                                    // (guests exist because everybody else is busy: nothing to spread)
-    a.main_waves = s.grid > gwaves ? s.grid - gwaves : s.grid;
-    a.launch_id = s.g_launch_id + 1;
-    (void)hipGetLastError();
-    tsx_launch_zstd_service(s.st_g, s.hd, s.d, gwaves, a);
-    if (hipGetLastError() != hipSuccess) return;                         // (no guests this time)
-    s.g_launch_id = a.launch_id; s.g_launched = true; s.guest_launches++;
-#else
-    (void)s;
-#endif
-}
-
-static void svc_destroy(tsx_device& d) {
-    if (!d.svc) return;
-    tsx_service& s = *d.svc;
-    if (s.h) __atomic_store_n(&s.h->stop, 1u, __ATOMIC_RELEASE);
-    if (s.st) { (void)hipStreamSynchronize(s.st); (void)hipStreamDestroy(s.st); }
-    if (s.st_g) { (void)hipStreamSynchronize(s.st_g); (void)hipStreamDestroy(s.st_g); }
-    for (void* p : s.deferred_dev) (void)hipFree(p);
-    for (void* p : s.deferred_host) (void)hipHostFree(p);
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.h_zero) (void)hipHostFree(s.h_zero);
-    if (s.d) (void)hipFree(s.d);
-    d.svc.reset();
-}
-
-// The queue, the device words and - from a probe launch that covers the chip - the CU keys that exist and the ones the compressor leaves alone.
-static int svc_create(tsx_device& d, int cus) {
-    std::unique_ptr<tsx_service> sp(new (std::nothrow) tsx_service);
-    if (!sp) return TSX_E_NOMEM;
-    d.svc = std::move(sp);
-    tsx_service& s = *d.svc;
-    HIPCHK(hipHostMalloc((void**)&s.h, sizeof(tsx_svc_host), hipHostMallocMapped | hipHostMallocPortable));
-    memset(s.h, 0, sizeof(tsx_svc_host));
-    s.h->yield = 1;                                                      // (cleared when a member is published on a quiet device: svc_note_quiet_locked)
-    HIPCHK(hipHostGetDevicePointer((void**)&s.hd, s.h, 0));
-    HIPCHK(hipHostMalloc((void**)&s.h_zero, 64, hipHostMallocDefault));
-    memset(s.h_zero, 0, 64);
-    HIPCHK(hipMalloc((void**)&s.d, sizeof(tsx_svc_dev)));
-    HIPCHK(hipMemset(s.d, 0, sizeof(tsx_svc_dev)));
-    // The service's stream gets the LOWEST stream priority of the device.  Two reasons: the runtime keeps a pool of hardware queues per
-    // priority and multiplexes a process's streams onto them - a stream that shared the service's hardware queue would sit behind a kernel
-    // that lives as long as uploads go on, and nothing else in this library (or, normally, in the process) creates low-priority streams;
-    // and between a compressor wave and a fetch's workgroup that could both be placed, the fetch's goes first.
-    {
-        int least = 0, greatest = 0;
-        if (g_cfg.svc_normal_priority || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least == greatest ||
-            hipStreamCreateWithPriority(&s.st, hipStreamNonBlocking, least) != hipSuccess) {
-            (void)hipGetLastError();
-            s.st = nullptr;
-            HIPCHK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-        }
-    }
-    {   // ... and the guests' stream, of the same (lowest) priority: a hardware queue of its own in that pool (a second stream of normal priority would
-        // share hardware queues with the fetch side's streams - and a kernel that lives for seconds blocks whatever is queued behind it)
-        int least = 0, greatest = 0;
-        if (g_cfg.svc_normal_priority || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least == greatest ||
-            hipStreamCreateWithPriority(&s.st_g, hipStreamNonBlocking, least) != hipSuccess) { (void)hipGetLastError(); s.st_g = nullptr; }     // (no guests then)
-    }
-    for (uint32_t i = TSX_SVC_MEMBERS; i-- > 0;) s.free_slots.push_back((uint16_t)i);
-    // which compute units are there?  (HIP promises nothing about placement: a launch of three 48 KiB workgroups per CU that stay ~30 us each
-    // has to spread over all of them; twice, in case the first one met a chip that was busy)
-    std::vector<uint32_t> seen(128, 0);
-    for (int pass = 0; pass < 2; pass++) {
-        (void)hipGetLastError();
-        tsx_launch_cu_probe(s.st, s.d, (uint32_t)cus * 3u * 2u);
-        HIPCHK(hipStreamSynchronize(s.st));
-        HIPCHK(hipMemcpy(seen.data(), s.d->seen, 512, hipMemcpyDeviceToHost));
-        uint32_t k = 0; for (uint32_t w : seen) k += (uint32_t)__builtin_popcount(w);
-        s.cu_keys = k;
-        if ((int)k >= cus) break;
-    }
-    s.cus = (uint32_t)cus;
-    // The reservation: ONE CU OF EVERY SHADER ENGINE first.  The hardware hands a kernel's workgroups to the shader engines in a fixed
-    // rotation and a workgroup waits for room in ITS engine: next to waves that stay for seconds, a fetch kernel's workgroup that falls to
-    // an engine without a free CU waits until the compressor launch ends (measured: kernels of a fetch each stuck for exactly one service
-    // launch, with 8 reserved CUs as well as with a CU mask that kept the service off 8 CUs - profiles/r05_kernel_trace_blocked_fetch.csv.gz,
-    // r05_cu_mask_variant_phases.txt).  A key's upper bits name the engine: xcc_id | se_id | sh_id (key >> 4).  Round r takes the r-th
-    // highest CU of every engine: the default (0xFFFFFFFF = "one per engine") stops after round 0; a number asked for is spread the same way.
-    // Never more than a quarter of the chip, and nothing at all when the probe did not find one key per CU (a key that stood for two CUs
-    // would take both).
-    std::vector<uint32_t> res(128, 0);
-    uint32_t engines = 0;
-    for (uint32_t g = 0; g < 256; g++) { bool any = false; for (uint32_t c = 0; c < 16; c++) { const uint32_t key = g << 4 | c; any |= ((seen[key >> 5] >> (key & 31)) & 1) != 0; } engines += any; }
-    s.engines = engines;
-    uint32_t want = g_cfg.reserved_cus == 0xFFFFFFFFu ? engines : g_cfg.reserved_cus;
-    if (want > s.cus / 4) want = s.cus / 4;
-    if (s.cu_keys != s.cus) {
-        if (g_cfg.debug || want) fprintf(stderr, "[tsxform] device %d: %u CU keys seen for %u compute units - no CU reservation\n", d.hip_id, s.cu_keys, s.cus);
-        want = 0;
-    }
-    uint32_t taken = 0;
-    for (uint32_t round = 0; taken < want && round < 16; round++)
-        for (uint32_t g = 0; g < 256 && taken < want; g++) {
-            uint32_t nth = 0;
-            for (int c = 15; c >= 0; c--) {
-                const uint32_t key = g << 4 | (uint32_t)c;
-                if (!((seen[key >> 5] >> (key & 31)) & 1)) continue;
-                if (nth++ == round) { res[key >> 5] |= 1u << (key & 31); taken++; break; }
-            }
-        }
-    s.cus_reserved = taken;
-    HIPCHK(hipMemcpy(s.d->reserved, res.data(), 512, hipMemcpyHostToDevice));
-    // A launch covers the chip exactly once - never more workgroups than are resident at the same time.  The waves stay for as long as there
-    // is work, so workgroups that did not fit would stay PENDING for as long, and a dispatch that is still in progress holds its hardware
-    // pipe: the first command of every stream whose queue sat on that pipe did not start until the launch was over.  Measured (gpurun
-    // r05a-r05n, profiles/r05_service_resident_waves_and_pending_workgroups.txt): launches of 256 x 24 against the 256 x 21 that fit (the
-    // kernel's 6704 bytes of LDS are allocated as 7680) kept 768 workgroups pending, and a fetch issued meanwhile came back when the launch
-    // ended - up to its age limit later.
-    // How many fit is MEASURED: a launch of 32 workgroups per CU whose waves stay until no workgroup has ARRIVED for 2 ms counts the most that
-    // were ever resident at once (registers, LDS with its allocation granularity, scratch slots - whatever limits it; the runtime's occupancy
-    // query said 24 where 21 fit).  The window was 500 us for most of round 6: the last few dozen workgroups of such a launch can arrive later
-    // than that behind the others (6094 - 6133 resident "measured" on a chip that holds 6144), the division below rounded that down to 23 per
-    // CU, and the service ran with 5888 waves instead of 6144 in most processes of some boxes - the "boxes that hold 23": they do not.  With
-    // 2 ms every pass sees 6137 - 6144 and the best of the passes is 6144 (four processes of four).  Up to four passes, until the best is a
-    // whole number of workgroups per CU twice in a row or at all after the second pass.  tsx_init runs on a device this process is not using yet.
-    for (int pass = 0; pass < 4; pass++) {
-        // (twice at least: the first launch of a process also loads the code object)
-#ifdef HIPEMU
-        tsx_svc_launch c{}; c.launch_id = ++s.launch_id; c.calibrate_ticks = 50000;       // (the CPU harness runs the workgroups one after the other: each waits its window out)
-#else
-        tsx_svc_launch c{}; c.launch_id = ++s.launch_id; c.calibrate_ticks = 200000;      // leave when nobody has arrived for 2 ms
-#endif
-        (void)hipGetLastError();
-        tsx_launch_zstd_service(s.st, s.hd, s.d, s.cus * 32u, c);
-        HIPCHK(hipStreamSynchronize(s.st));
-        uint32_t lm[2] = {0, 0};
-        HIPCHK(hipMemcpy(lm, &s.d->live, 8, hipMemcpyDeviceToHost));
-        const uint32_t before = s.resident;
-        if (lm[1] > s.resident) s.resident = lm[1];
-        HIPCHK(hipMemcpy(&s.d->live_max, s.h_zero, 4, hipMemcpyHostToDevice));
-        if (g_cfg.debug) fprintf(stderr, "[tsxform] device %d: calibration launch %d: %u workgroups resident at once\n", d.hip_id, pass, lm[1]);
-        if (pass >= 1 && (lm[1] == before || s.resident % s.cus == 0)) break;
-    }
-    const uint32_t usable = s.cus;
-    uint32_t per_cu = g_cfg.svc_waves_per_cu ? g_cfg.svc_waves_per_cu : s.resident / usable;
-    if (per_cu == 0 || per_cu > 32) per_cu = 16;                        // (a measurement that cannot be: stay on the safe side)
-    s.waves_per_cu = per_cu;
-    s.grid = usable * per_cu;
-    return TSX_OK;
-}
-
-// Frees that must not wait for the service kernel: freed at once when it is known to be gone (mu held meanwhile: no launch can begin),
-// otherwise when its end is seen (svc_running_locked) or at shutdown.
-static void svc_free_dev(tsx_device* dev, void* p) {
-    if (!p) return;
-    if (!dev->svc) { (void)hipFree(p); return; }
-    std::lock_guard<std::mutex> lk(dev->svc->mu);
-    if (svc_alive_locked(*dev->svc)) dev->svc->deferred_dev.push_back(p); else (void)hipFree(p);
-}
-static void svc_free_host(tsx_device* dev, void* p) {
-    if (!p) return;
-    if (!dev->svc) { (void)hipHostFree(p); return; }
-    std::lock_guard<std::mutex> lk(dev->svc->mu);
-    if (svc_alive_locked(*dev->svc)) dev->svc->deferred_host.push_back(p); else (void)hipHostFree(p);
-}
-
-// Memory management that needs the memory BACK (an allocation has failed): no launches until svc_resume, the running kernel is told to
-// stop (its waves leave after their current chunk, <= ~1.3 s), deferred frees happen.  Members that wait meanwhile just wait.
-static void svc_pause(tsx_device* dev) {
-    if (!dev->svc) return;
-    tsx_service& s = *dev->svc;
-    std::unique_lock<std::mutex> lk(s.mu);
-    s.paused++;
-    __atomic_store_n(&s.h->stop, 1u, __ATOMIC_RELEASE);
-    s.stop_dirty = true;
-    while (svc_alive_locked(s)) { lk.unlock(); std::this_thread::sleep_for(std::chrono::microseconds(200)); lk.lock(); }
-}
-// The safety net of the fetch side.  One CU of every shader engine is kept free for it, and a fetch next to saturating uploads takes its
-// ~2 ms - but once in a few hundred fetches (measured: 1 of 271, 2 of 12, 0 of 218 + 218 in four runs) a kernel of a fetch did not start
-// until the compressor launch next to it ended, for a reason that was not found.  A batch that has waited for its own kernels for 200 ms
-// while the service kernel is alive asks that launch to end: its waves leave after their current chunk (<= ~1.3 s), the waiting callers'
-// watchdog starts the next one, and the fetch gets the chip in between.  Cost: one chunk time of a half-empty chip, only when it happens.
-static void svc_rotate(tsx_device* dev) {
-    if (!dev->svc) return;
-    tsx_service& s = *dev->svc;
-    std::lock_guard<std::mutex> lk(s.mu);
-    if (s.rotating || s.paused || !svc_running_locked(s)) return;
-    s.rotating = true; s.rotations++;
-    __atomic_store_n(&s.h->stop, 1u, __ATOMIC_RELEASE);
-    s.stop_dirty = true;
-}
-// Waits for an event of a batch that is NOT the compressor's, with that safety net.
+// Waits for an event of a batch that is NOT the compressor's, with the safety net of svc_rotate.
 static hipError_t wait_event_watching(tsx_ctx* c, hipEvent_t ev) {
     const auto t0 = std::chrono::steady_clock::now();
     bool asked = false;
@@ -578,22 +149,13 @@ static hipError_t wait_event_watching(tsx_ctx* c, hipEvent_t ev) {
         if (e != hipErrorNotReady) return e;
         (void)hipGetLastError();
         const auto age = std::chrono::steady_clock::now() - t0;
-        if (!asked && age > std::chrono::milliseconds(200)) { svc_rotate(c->dev); asked = true; }
+        if (!asked && age > std::chrono::milliseconds(SVC_ROTATE_AFTER_MS)) { svc_rotate(c->dev); asked = true; }
         // A single-chunk fetch is 1.6 ms.  Only the first 200 us are polled without a sleep (a piece that is nearly done); after that the thread
         // sleeps between looks - 20 us while the batch is young (a sleep's real granularity is ~60 us: + <= 4 % on a single-chunk fetch), 50 us up
         // to 20 ms, 500 us beyond.  Every ChunkCache worker (ForkJoinPool, parallelism = #cores by default) waits in here: round 5 spun for 3 ms,
         // i.e. a whole core per fetch in flight.
         if (age > std::chrono::microseconds(200))
             std::this_thread::sleep_for(std::chrono::microseconds(age > std::chrono::milliseconds(20) ? 500 : age > std::chrono::milliseconds(3) ? 50 : 20));
-    }
-}
-static void svc_resume(tsx_device* dev) {
-    if (!dev->svc) return;
-    tsx_service& s = *dev->svc;
-    std::lock_guard<std::mutex> lk(s.mu);
-    if (s.paused && --s.paused == 0) {
-        __atomic_store_n(&s.h->stop, 0u, __ATOMIC_RELEASE);
-        if (!s.out.empty() && !svc_running_locked(s)) (void)svc_launch_locked(s);     // (a failure shows up in the waiting members' watchdog)
     }
 }
 
@@ -690,10 +252,11 @@ extern "C" int tsx_init_ex(int device_count, const int* device_ids, const tsx_co
     if (rc != TSX_OK) { for (auto& d : devs) device_free_consts(d); return rc; }   // nothing of a failed init stays allocated
     g_devs.swap(devs);
     char* vb = g_version_buf[g_version_gen++ & 1];
+    const svc_geometry sg = svc_geometry_of(g_devs[0]);
     snprintf(vb, sizeof g_version_buf[0],
              "tsxform 0.5 (gfx950 HIP; CRC32C, AES-256-GCM, Zstd frames of levels 1-3; zstd parity target libzstd 1.5.7 / 1.5.6 profile; %d device(s): %s; "
              "compressor service: %u waves, %u of %u CUs reserved for fetches)",
-             (int)g_devs.size(), g_devs[0].name, g_devs[0].svc->grid, g_devs[0].svc->cus_reserved, g_devs[0].svc->cus);
+             (int)g_devs.size(), g_devs[0].name, sg.waves, sg.cus_reserved, sg.cus);
     g_version.store(vb, std::memory_order_release);
     return (int)g_devs.size();
 }
@@ -1154,148 +717,6 @@ struct tsx_run {                                              // what one batch 
     const uint8_t* d_src; uint8_t* d_dst;
 };
 
-// ---- service: members ---------------------------------------------------------------------------------------------------------------
-// Publish one member: `proto` names its buffers (n, done and flag included); its n chunks become the next n tickets.  Returns the member's
-// id (for svc_retire) through *id.  Blocks while the ticket ring or the member slots are full (members retire one by one).
-static int svc_submit(tsx_device* dev, const tsx_zseg& proto, const uint32_t* h_flag, uint64_t* id) {
-    tsx_service& s = *dev->svc;
-    const uint32_t n = proto.n;
-    if (!n || n > TSX_SVC_MEMBER_MAX) return TSX_E_INVAL;
-    std::unique_lock<std::mutex> lk(s.mu);
-    // room: a ticket record is reused TSX_SVC_TICKETS tickets later - by then every member up to it must be complete ON THE DEVICE (its flag
-    // raised; whether its caller has come back for it yet does not matter: a caller that publishes its pieces one after the other must
-    // never wait here for a piece of its own that only it can retire)
-    for (;;) {
-        uint32_t oldest = s.published; bool any = false;
-        for (const auto& m : s.out) if (!m.done && !__atomic_load_n(m.h_flag, __ATOMIC_ACQUIRE)) { oldest = m.first; any = true; break; }
-        if (!s.free_slots.empty() && (!any || (uint32_t)(s.published + n - oldest) <= TSX_SVC_TICKETS)) break;
-        // whoever waits for room is also the service's watchdog (as svc_wait is): the kernel may have ended - idle, age limit, a rotation -
-        // with the members that hold the room still unserved, and their callers may all be in here
-        if (!s.paused && !s.out.empty() && !svc_running_locked(s)) { s.watchdog_launches++; (void)svc_launch_locked(s); }
-        s.cv.wait_for(lk, std::chrono::milliseconds(1));
-    }
-    svc_note_quiet_locked(s);
-    const uint16_t slot = s.free_slots.back(); s.free_slots.pop_back();
-    const uint16_t gen = ++s.slot_gen[slot];
-    tsx_zseg e = proto;
-    e.gen = gen;
-    s.h->member[slot] = e;
-    const uint32_t first = s.published;
-    for (uint32_t i = 0; i < n; i++) { tsx_svc_ticket& t = s.h->ticket[(first + i) & (TSX_SVC_TICKETS - 1)]; t.member_gen = (uint32_t)gen << 16 | slot; t.chunk = i; }
-    s.published = first + n;
-    __atomic_store_n(&s.h->published, s.published, __ATOMIC_RELEASE);   // the waves' poll picks it up (a few microseconds)
-    *id = s.next_id++;
-    s.out.push_back({*id, first, n, slot, false, h_flag});
-    s.members++;
-    if (!svc_running_locked(s)) { const int rc = svc_launch_locked(s); if (rc == TSX_OK) svc_try_guests_locked(s); return rc; }     // (on failure the caller abandons the member: svc_retire)
-    svc_try_guests_locked(s);                                           // the queue has just grown: deeper than the launch has waves?  (and quiet?)
-    return TSX_OK;
-}
-
-// The member is over - completed, or abandoned (`abandon`: its tickets, should a later launch ever reach them, name a stale generation).
-static void svc_retire(tsx_device* dev, uint64_t id, bool abandon) {
-    tsx_service& s = *dev->svc;
-    std::lock_guard<std::mutex> lk(s.mu);
-    for (auto& m : s.out) if (m.id == id) {
-        m.done = true;
-        if (abandon) { s.slot_gen[m.slot]++; __atomic_store_n(&s.h->member[m.slot].gen, (uint32_t)s.slot_gen[m.slot], __ATOMIC_RELEASE); }
-        else s.chunks += m.n;
-        break;
-    }
-    while (!s.out.empty() && s.out.front().done) { s.free_slots.push_back(s.out.front().slot); s.out.pop_front(); }
-    s.cv.notify_all();
-}
-
-// Wait for a member's flag.  A chunk takes about a second: short sleeps only while the member is young (tests, tiny chunks), a
-// millisecond between looks afterwards - dozens of callers must not burn the cores next to the GPU's NUMA node.  Every look that follows
-// a real sleep is also the service's watchdog: a kernel that has ended with this member unfinished is started again.
-static int svc_wait(tsx_device* dev, uint32_t* h_flag) {
-    tsx_service& s = *dev->svc;
-    const auto t0 = std::chrono::steady_clock::now();
-    uint32_t failures = 0;
-    for (uint32_t look = 0;; look++) {
-        if (__atomic_load_n(h_flag, __ATOMIC_ACQUIRE)) return TSX_OK;
-        const auto age = std::chrono::steady_clock::now() - t0;
-        const bool young = age < std::chrono::milliseconds(2);
-        if (!young || (look & 7) == 7) {
-            std::lock_guard<std::mutex> lk(s.mu);
-            if (!s.paused && !svc_running_locked(s)) {
-                if (__atomic_load_n(h_flag, __ATOMIC_ACQUIRE)) return TSX_OK;
-                s.watchdog_launches++;
-                if (svc_launch_locked(s) != TSX_OK && ++failures >= 3) return TSX_E_DEVICE;
-            } else if (!young) svc_try_guests_locked(s);                // (the callers may all be in here: whoever waits also asks whether guests are due)
-        }
-        std::this_thread::sleep_for(young ? std::chrono::microseconds(20) : age < std::chrono::milliseconds(50) ? std::chrono::microseconds(250) : std::chrono::microseconds(1000));
-    }
-}
-
-// Returns when the device's service kernel has ended (its waves leave a moment after the last chunk): measurement tools bracket a timed
-// region with it so that the region's chunks and the kernel launches that did them can be set against each other (tsx_service_stats).
-extern "C" int tsx_service_quiesce(int device_index) {
-    tsx_device* dev;
-    { std::lock_guard<std::mutex> lk(g_mu); if (device_index < 0 || device_index >= (int)g_devs.size()) return TSX_E_INVAL; dev = &g_devs[device_index]; }
-    tsx_service& s = *dev->svc;
-    for (;;) {
-        { std::lock_guard<std::mutex> lk(s.mu); if (!svc_alive_locked(s)) return TSX_OK; }
-        std::this_thread::sleep_for(std::chrono::microseconds(100));
-    }
-}
-
-static_assert(sizeof(tsx_service_info) == 112, "relocated_waves took the struct's tail padding: callers compiled before it hand in 112 bytes too");
-extern "C" int tsx_service_stats(int device_index, tsx_service_info* out) {
-    if (!out) return TSX_E_INVAL;
-    tsx_device* dev;
-    { std::lock_guard<std::mutex> lk(g_mu); if (device_index < 0 || device_index >= (int)g_devs.size()) return TSX_E_INVAL; dev = &g_devs[device_index]; }
-    tsx_service& s = *dev->svc;
-    tsx_device_scope keep;
-    if (hipSetDevice(dev->hip_id) != hipSuccess) return TSX_E_DEVICE;
-    std::lock_guard<std::mutex> lk(s.mu);
-    const bool running = svc_running_locked(s);
-    memset(out, 0, sizeof *out);
-    out->launches = s.launches; out->watchdog_launches = s.watchdog_launches; out->rotations = (uint32_t)s.rotations; out->members = s.members; out->chunks = s.chunks;
-    out->kernel_ms = s.kernel_ms; out->running = running ? 1u : 0u;
-    out->waves = s.grid; out->compute_units = s.cus; out->cu_keys_seen = s.cu_keys; out->reserved_cus = s.cus_reserved; out->shader_engines = s.engines;
-    out->guest_launches = (uint32_t)s.guest_launches; out->readmissions = (uint32_t)s.readmissions;
-    if (running) {
-        // the launch is alive: the words its waves mirror into pinned memory (a copy out of device memory is a blit kernel for sizes like
-        // these and, next to guest waves, waits for the launch to end - tsx_internal.h, tsx_svc_host.m_*)
-        out->device_chunks = __atomic_load_n(&s.h->m_chunks, __ATOMIC_RELAXED); out->live_waves = __atomic_load_n(&s.h->m_live, __ATOMIC_RELAXED);
-        out->live_waves_max = __atomic_load_n(&s.h->m_live_max, __ATOMIC_RELAXED); out->wave_starts = __atomic_load_n(&s.h->m_wave_starts, __ATOMIC_RELAXED);
-        out->reserved_exits = __atomic_load_n(&s.h->m_reserved_exits, __ATOMIC_RELAXED); out->skipped_tickets = __atomic_load_n(&s.h->m_skipped, __ATOMIC_RELAXED);
-        out->yielded_waves = __atomic_load_n(&s.h->m_yields, __ATOMIC_RELAXED); out->returned_chunks = __atomic_load_n(&s.h->m_returned, __ATOMIC_RELAXED);
-        out->relocated_waves = __atomic_load_n(&s.h->m_relocated, __ATOMIC_RELAXED);
-        return TSX_OK;
-    }
-    uint32_t w[4] = {0, 0, 0, 0};
-    if (hipMemcpy(w, &s.d->stat_yields, 8, hipMemcpyDeviceToHost) == hipSuccess) { out->yielded_waves = w[0]; out->returned_chunks = w[1]; } else (void)hipGetLastError();
-    if (hipMemcpy(w, &s.d->stat_chunks, sizeof w, hipMemcpyDeviceToHost) == hipSuccess) {
-        out->device_chunks = w[0]; out->wave_starts = w[1]; out->reserved_exits = w[2]; out->skipped_tickets = w[3];
-    } else (void)hipGetLastError();
-    if (hipMemcpy(w, &s.d->live, 8, hipMemcpyDeviceToHost) == hipSuccess) { out->live_waves = w[0]; out->live_waves_max = w[1]; } else (void)hipGetLastError();
-    if (hipMemcpy(w, &s.d->stat_relocated, 4, hipMemcpyDeviceToHost) == hipSuccess) out->relocated_waves = w[0]; else (void)hipGetLastError();
-    return TSX_OK;
-}
-
-// Test hook (not part of the ABI): put the device's ticket counters at `published` (an idle service only) - the wrap-around of the 32-bit
-// counters is ten days of full-rate compression away otherwise.
-extern "C" int tsx_debug_service_seed(int device_index, uint32_t published) {
-    tsx_device* dev;
-    { std::lock_guard<std::mutex> lk(g_mu); if (device_index < 0 || device_index >= (int)g_devs.size()) return TSX_E_INVAL; dev = &g_devs[device_index]; }
-    tsx_service& s = *dev->svc;
-    tsx_device_scope keep;
-    if (hipSetDevice(dev->hip_id) != hipSuccess) return TSX_E_DEVICE;
-    std::lock_guard<std::mutex> lk(s.mu);
-    if (svc_alive_locked(s) || !s.out.empty()) return TSX_E_INVAL;
-    const uint32_t w[2] = {published, published};
-    if (hipMemcpy(&s.d->next, w, 8, hipMemcpyHostToDevice) != hipSuccess) return TSX_E_DEVICE;      // next, pub
-    const uint32_t fa[2] = {published, 0};
-    static_assert(offsetof(tsx_svc_dev, avail) == offsetof(tsx_svc_dev, fin) + 4, "fin, avail");
-    if (hipMemcpy(&s.d->fin, fa, 8, hipMemcpyHostToDevice) != hipSuccess) return TSX_E_DEVICE;      // fin, avail (nothing outstanding: no right to a ticket)
-    s.published = published;
-    __atomic_store_n(&s.h->published, published, __ATOMIC_RELEASE);
-    return TSX_OK;
-}
-
 // Can the device address ALL of [p, p + bytes)?  Zero-copy output lets the compressor waves write there; a buffer of which only a
 // prefix is registered, or that spans two registrations, would fault the process (the broker's JVM) at the first byte behind the
 // mapping.  Known extents only: a range inside ONE tsx_host_register'ed buffer, or inside one allocation the runtime reports
@@ -1567,7 +988,7 @@ static int launch_stages(const tsx_run& r, const tsx_sub& sb, hipEvent_t* e, hip
             // (a batch decode next to running uploads takes the scratch-free build of the chunk-serial kernel: a dispatch that needs scratch
             //  waits for the compressor service's kernel - and its scratch - to go away)
             bool busy_service = false;
-            if (!skip) { std::lock_guard<std::mutex> lk(c->dev->svc->mu); busy_service = svc_running_locked(*c->dev->svc) || !c->dev->svc->out.empty(); }
+            if (!skip) busy_service = svc_busy(c->dev);
             t.unzstd_launches += tsx_launch_zstd_decompress(st, c->dev->d_zc, zsrc, r.enc ? 1 : 0, (uint64_t)c->mid_stride, dd, n, r.d_dst, ds, dzw, skip, skip_stride, busy_service);
         } else if (!r.enc) {
             uint32_t bpc = r.max_len > (1u << 20) ? 16 : 1;

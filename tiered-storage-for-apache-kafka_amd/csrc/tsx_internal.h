@@ -70,7 +70,7 @@ struct tsx_chain_fuse {          // stages the compressor wave of chunk i runs i
                                  // before the GCM tail and wipes that copy afterwards (no upload, no device-side wipe: nothing but the launch)
 };
 
-struct tsx_zseg {                // one caller's batch ("member") in the device's compressor service queue (zstd_service_kernel, tsx_api.hip)
+struct tsx_zseg {                // one caller's batch ("member") in the device's compressor service queue (zstd_service_kernel, tsx_service.hip)
     uint32_t n, profile;         // chunks 0 .. n - 1 of the batch; TSX_ZSTD_PROFILE_*
     uint32_t gen, level;         // generation of this member slot: a ticket that names an older generation is skipped (abandoned member);
                                  // Zstandard level of the member's frames: 1, 2, or anything else = 3
@@ -83,6 +83,7 @@ struct tsx_zseg {                // one caller's batch ("member") in the device'
 };
 
 // ---- the compressor service: one device-wide work queue, persistent waves --------------------------------------------------------
+// (the waves' side of the protocol: svc_dev.h; the host's side: tsx_service.hip)
 // Every compressing batch of a device - whichever thread or context it comes from - is a MEMBER of that device's queue: the host
 // appends one ticket per chunk (ticket -> member slot + chunk index) to a ring in pinned host memory and publishes the new end of the
 // ring; the waves of zstd_service_kernel take tickets one by one (a device-side counter), compress (+ checksum + encrypt) the chunk and
@@ -127,7 +128,6 @@ struct tsx_svc_dev {                 // device memory: the waves' shared state
     uint32_t busy;                   // waves that hold a ticket
     uint32_t poll_stamp;             // low 32 bits of the 100 MHz clock at the last host poll
     uint32_t stop;                   // mirror of tsx_svc_host.stop
-    uint32_t gen_start_lo, gen_start_hi, gen_started;   // clock at the first wave of this launch (generation age)
     uint32_t stat_chunks, stat_wave_starts, stat_reserved_exits, stat_skipped;
     uint32_t entered, exited;        // waves of the current launch that have started / left (the last one to leave reports the launch's end)
     uint32_t t_first_lo, t_first_hi; // clock at the first wave's start
@@ -169,7 +169,6 @@ struct tsx_svc_launch {              // kernel arguments that shape a launch
     uint32_t spread_cus;             // != 0: compute units a partial load is spread over (the ones the compressor uses); 0 = tickets go to whoever asks first
     uint32_t guest_idle_ticks;       // a guest that has found the queue dry for this long leaves when the chip is mostly idle (a chip whose every slot is held by mostly IDLE waves slows the busy ones down)
     uint32_t main_waves;             // guest launches: the waves of the launch they help - while more than half of them are busy a guest waits out a dry queue (50 x guest_idle_ticks)
-    uint32_t idle_nap_max;           // longest nap of an idle wave between two looks at the queue, in 3.5 us (0 = 64: 224 us)
     uint32_t keep_waves;             // waves that stay on a reserved CU all the same (0 = the CU is left alone; the rest of it - LDS, registers, wave slots - is the room a fetch's workgroups find)
 };
 void tsx_launch_zstd_service(hipStream_t st, tsx_svc_host* hd, tsx_svc_dev* d, uint32_t grid, tsx_svc_launch a);
