@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import tsxform
+from tests import fuzz_cases as fc
 from tests import level_cases as lc
 from tests import parity_cases as pc
 from tests import zstd_inspect as zi
@@ -162,6 +163,64 @@ def test_differential_fuzz_levels_1_and_2(emu, oracle):
         outs, d = lc.run_transform(emu, nat.COMPRESS, part, level)
         for i, x in enumerate(part):
             assert d["status"][i] == 0 and outs[i] == oracle.zstd_compress_chunk(x.tobytes(), level), (level, i, x.size)
+
+
+# ---- past the window, shared buckets, acceleration (tests/fuzz_cases.py; the same generators at full count on the device) ----
+def _frames_equal_libzstds_and_decode(emu, oracle, chunks, level, what):
+    outs, d = lc.run_transform(emu, nat.COMPRESS, chunks, level)
+    for i, x in enumerate(chunks):
+        assert d["status"][i] == 0, (what, level, i, x.size)
+        assert outs[i] == oracle.zstd_compress_chunk(x.tobytes(), level), "%s case %d (%d bytes): level %d frame differs from libzstd" % (what, i, x.size, level)
+    lc.check_roundtrip(emu, nat.COMPRESS, chunks, outs)
+
+
+@pytest.mark.parametrize("level", [1, 2])
+def test_matches_that_straddle_the_windows_low_edge(emu, oracle, level):
+    """16 inputs longer than the level's window (512 KiB / 1 MiB) in which a copy's partner crosses the lowest valid index of a block:
+    prefixStartIndex, the candidate test against it, the backward count's limit.  First the guard, from libzstd's frames alone: at least
+    half of the inputs make libzstd emit an offset within 4096 of the window size (seeds 20261018 / 20261019: 12 of 16 at either level,
+    7 and 6 within 64) - else the generator has stopped reaching the edge and the comparison below proves little."""
+    _need157(oracle)
+    W = fc.LEVEL_WINDOW[level]
+    rng = np.random.default_rng(20261017 + level)
+    chunks = [fc.straddle_case(rng, W) for _ in range(16)]
+    near = [fc.offsets_near_window(oracle.zstd_compress_chunk(x.tobytes(), level), W) for x in chunks]
+    reached = sum(1 for n in near if n)
+    print("level %d: %d of %d straddle inputs have a libzstd offset in (W - 4096, W]" % (level, reached, len(chunks)))
+    assert 2 * reached >= len(chunks), near
+    _frames_equal_libzstds_and_decode(emu, oracle, chunks, level, "straddle")
+
+
+@pytest.mark.parametrize("level", [1, 2])
+def test_structured_inputs_longer_than_the_window(emu, oracle, level):
+    """gen_case beyond the window: ZSTD_window_enforceMaxDist in the chunk loop, repcodes a slide invalidates at a block's start."""
+    _need157(oracle)
+    rng = np.random.default_rng(20261027 + level)
+    chunks = [fc.level_case(rng, level, "big") for _ in range(4)]
+    assert all(x.size >= fc.LEVEL_WINDOW[level] for x in chunks)
+    _frames_equal_libzstds_and_decode(emu, oracle, chunks, level, "big")
+
+
+@pytest.mark.parametrize("level", [1, 2])
+def test_shared_buckets_and_accelerated_steps_over_several_blocks(emu, oracle, level):
+    """6 collision-rich inputs (lanes of one wave step in one bucket: the earlier lane's position is the candidate, the last lane's the
+    write) and 6 with incompressible stretches that push the step to 2, 3, 4, 5 ... before a match on either position of a pair (the
+    write of the following position that libzstd makes for steps up to 4), 300 - 420 KB each: three blocks and more."""
+    _need157(oracle)
+    rng = np.random.default_rng(20261037 + level)
+    chunks = [fc.level_case(rng, level, "collision") for _ in range(6)] + [fc.level_case(rng, level, "accel") for _ in range(6)]
+    assert all(x.size > 2 * fc.BLOCK for x in chunks)
+    _frames_equal_libzstds_and_decode(emu, oracle, chunks, level, "collision/accel")
+
+
+def test_level_2_is_dfast_between_128_and_256_KiB(emu, oracle):
+    """The double-fast parser with level 2's own parameters (windowLog 18, both tables 2^14, minMatch 5): structured inputs over the band,
+    its first and its last size included."""
+    _need157(oracle)
+    rng = np.random.default_rng(20261047)
+    sizes = [131073, 262144] + [int(rng.integers(131074, 262144)) for _ in range(6)]
+    chunks = [fc.gen_case(rng, s) for s in sizes]
+    _frames_equal_libzstds_and_decode(emu, oracle, chunks, 2, "dfast band")
 
 
 # ---- service: levels side by side, hand-back ------------------------------------------------------------------------------

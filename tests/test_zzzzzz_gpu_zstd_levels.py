@@ -1,6 +1,8 @@
 """Zstandard levels 1 and 2 on the device: full-size chunks byte for byte libzstd 1.5.7's at the same level, the full chain against the
-oracle, a 256-chunk B segment at level 1, levels side by side from 16 threads, and level 1 next to a fetch that makes guest waves hand
-their chunks back.  (The logic, with small inputs, runs on the CPU emulator: tests/test_emu_zstd_levels.py.)"""
+oracle, a 256-chunk B segment at level 1, levels side by side from 16 threads, level 1 next to a fetch that makes guest waves hand
+their chunks back, and a differential fuzz of 464 inputs per level - past the window, collision-rich, accelerated - with the 1.5.6 profile
+over a part of them.  (The logic, with fewer inputs, runs on the CPU emulator: tests/test_emu_zstd_levels.py - which does not run a
+wave's lanes in lockstep: a lane that reads a table word another lane of its wave has just written is tested here alone.)"""
 import functools
 import threading
 import time
@@ -9,7 +11,10 @@ import numpy as np
 import pytest
 
 import tsxform
+from tests import fuzz_cases as fc
 from tests import level_cases as lc
+from tests import parity_cases as pc
+from tests import zstd_inspect as zi
 from tsxform import synth
 
 nat = tsxform._native
@@ -165,3 +170,79 @@ def test_level_1_next_to_a_fetch_while_guest_waves_run_it(gpu, oracle):
     assert not errors, errors
     assert min(rounds) >= 1, rounds
     print("level 1 under fetches: %d rounds, %d chunks handed back" % (sum(rounds), sv1["returned_chunks"] - sv0["returned_chunks"]))
+
+
+# ---- differential fuzz ---------------------------------------------------------------------------------------------------
+FUZZ_SEED = {1: 20261101, 2: 20261102}
+FUZZ_KINDS = (("small", 256), ("straddle", 96), ("big", 32), ("collision", 32), ("accel", 32))
+TAIL_DELTAS = (-16, -9, -8, -7, -3, -1, 0, 1, 2, 3, 6, 7, 8, 9, 10, 16)       # the last block: 1 .. 7 bytes (raw), 8 and a few more, or none
+
+
+@functools.lru_cache(maxsize=2)
+def _fuzz_cases(level):
+    """[(kind, input)] for `level` - built once, shared (unchanged) by the tests below."""
+    rng = np.random.default_rng(FUZZ_SEED[level])
+    cases = [(kind, fc.level_case(rng, level, kind)) for kind, n in FUZZ_KINDS for _ in range(n)]
+    W = fc.LEVEL_WINDOW[level]
+    cases += [("tail", fc.gen_case(rng, W + fc.BLOCK * (1 + i % 2) + dlt)) for i, dlt in enumerate(TAIL_DELTAS)]
+    return cases
+
+
+@functools.lru_cache(maxsize=2)
+def _fuzz_frames(level):
+    """libzstd's frames of _fuzz_cases(level)."""
+    from oracle import oracle as o
+    return [o.zstd_compress_chunk(x.tobytes(), level) for _, x in _fuzz_cases(level)]
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("level", [1, 2])
+def test_differential_fuzz_vs_libzstd_at_levels_1_and_2(gpu, oracle, level):
+    """Per level 256 structured inputs of 0 - 420 KB (both band edges among them), 96 whose far match straddles the low edge of the window
+    (512 KiB / 1 MiB), 32 structured ones longer than the window, 32 collision-rich, 32 with accelerated steps and 16 that end within 16
+    bytes of a block boundary: every frame is libzstd 1.5.7's at that level and the device decoder restores the input; the first 64 also
+    go through the full chain in the three memory kinds."""
+    _need157(oracle)
+    cases, frames = _fuzz_cases(level), _fuzz_frames(level)
+    assert len(cases) == 464
+    for lo in range(0, len(cases), 128):
+        part = [x for _, x in cases[lo:lo + 128]]
+        outs, d = lc.run_transform(gpu, nat.COMPRESS, part, level, mem="device")
+        back, d2 = pc.run_detransform(gpu, nat.COMPRESS, outs, [int(x.size) for x in part])
+        for i, x in enumerate(part):
+            what = "level %d seed %d case %d (%s, %d bytes)" % (level, FUZZ_SEED[level], lo + i, cases[lo + i][0], x.size)
+            assert d["status"][i] == 0, what
+            assert outs[i] == frames[lo + i], what + ": frame differs from libzstd"
+            assert d2["status"][i] == 0 and back[i] == x.tobytes(), what + ": the device decoder does not restore the input"
+    flags = nat.COMPRESS | nat.ENCRYPT | nat.CRC
+    first = [x for _, x in cases[:64]]
+    for mem in (None, "device", "packed"):
+        lc.check_vs_oracle(gpu, oracle, flags, first, level, mem=mem)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("level", [1, 2])
+def test_profile_1_5_6_at_levels_1_and_2_on_the_device(gpu, oracle, level):
+    """48 of the fuzz inputs (every kind) through ZSTD_PROFILE_1_5_6, the same parse without 1.5.7's pre-splitter: libzstd decodes every
+    frame back to the input, and where the pre-splitter cut nothing (every block of libzstd 1.5.7's frame but the last regenerates 128 KiB)
+    the frame is libzstd 1.5.7's, byte for byte.  Inputs of both sorts occur."""
+    _need157(oracle)
+    cases, frames = _fuzz_cases(level), _fuzz_frames(level)
+    pick = list(range(0, 256, 16)) + list(range(256, 352, 8)) + list(range(352, 448, 6)) + list(range(448, 464, 4))
+    assert len(pick) == 48
+    chunks = [cases[i][1] for i in pick]
+    outs, d = lc.run_transform(gpu, nat.COMPRESS, chunks, level, mem="device", profile=nat.ZSTD_PROFILE_1_5_6)
+    uncut = cut = 0
+    for k, i in enumerate(pick):
+        what = "level %d seed %d case %d (%s, %d bytes)" % (level, FUZZ_SEED[level], i, cases[i][0], chunks[k].size)
+        raw = chunks[k].tobytes()
+        assert d["status"][k] == 0, what
+        assert oracle.zstd_decompress_chunk(outs[k], len(raw)) == raw, what + ": libzstd does not decode the 1.5.6 frame to the input"
+        sizes = zi.block_sizes(frames[i])
+        if all(s == fc.BLOCK for s in sizes[:-1]):
+            uncut += 1
+            assert outs[k] == frames[i], what + ": nothing for the pre-splitter to cut, yet the 1.5.6 frame is not libzstd 1.5.7's"
+        else:
+            cut += 1
+    print("level %d, profile 1.5.6: %d inputs pinned to libzstd 1.5.7's bytes, %d where its pre-splitter cuts" % (level, uncut, cut))
+    assert uncut >= 1 and cut >= 1, (uncut, cut)

@@ -5,6 +5,8 @@ Every case: structured random input -> emulated zstd_compress_kernel (1.5.7 prof
 byte, the emulated decoder must restore the input, and the full chain (compress + GCM + CRC, both fused and separate
 launches) must match the oracle chain.  Test infrastructure only (uses oracle/ and tests/emu).
     python tools/fuzz_emu.py --seconds 3000 --seed 1 --out /tmp/fuzz1.log
+With --level 1 or 2 (strategy fast): frames against libzstd at that level and the decoder, on inputs from all of tests/fuzz_cases.py's
+generators - structured, collision-rich, accelerated, and (the "big" ones, sized from the level's window) straddling and structured.
 """
 import argparse
 import os
@@ -17,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tsxform  # noqa: E402
 from tests import parity_cases as pc  # noqa: E402
-from tests.fuzz_cases import gen_case  # noqa: E402
+from tests import level_cases as lc  # noqa: E402
+from tests.fuzz_cases import gen_case, level_case  # noqa: E402
 
 nat = tsxform._native
 
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--batch", type=int, default=6)
     ap.add_argument("--out", default="")
+    ap.add_argument("--level", type=int, choices=(1, 2, 3), default=3)
     ap.add_argument("--guests", action="store_true", help="fuzz the guest waves' hand-back instead: every launch's first workgroup sits on the reserved CU and is "
                                                           "made to give its chunk back at a random block; the full chain must still equal the oracle's")
     args = ap.parse_args()
@@ -41,6 +45,8 @@ def main():
     log = open(args.out, "a") if args.out else sys.stdout
     if args.guests:
         return fuzz_guests(args, emu, o, rng, log)
+    if args.level != 3:
+        return fuzz_fast(args, emu, o, rng, log)
     while time.time() - t0 < args.seconds:
         cases = [gen_case(rng) for _ in range(args.batch)]
         outs, d = pc.run_transform(emu, nat.COMPRESS, cases)
@@ -68,6 +74,37 @@ def main():
         if (n_cases // args.batch) % 10 == 0:
             print("[%6.0fs] seed %d: %d cases, %.1f MB, %d bad" % (time.time() - t0, args.seed, n_cases, n_bytes / 1e6, bad), file=log, flush=True)
     print("DONE seed %d: %d cases, %.1f MB, %d bad" % (args.seed, n_cases, n_bytes / 1e6, bad), file=log, flush=True)
+
+
+def fuzz_fast(args, emu, o, rng, log):
+    """Levels 1 and 2.  A batch is args.batch inputs: mostly gen_case's default sizes, one collision-rich or accelerated input of 300 - 420 KB,
+    and in every other batch a big one (straddling the window's low edge, or structured and W .. W + 300000 bytes long)."""
+    level = args.level
+    t0 = time.time(); n_cases = 0; n_bytes = 0; bad = 0; batches = 0
+    while time.time() - t0 < args.seconds:
+        kinds = ["small"] * max(args.batch - 2, 1) + [("collision", "accel")[batches % 2]] + ([("straddle", "big")[(batches // 2) % 2]] if batches % 2 else [])
+        cases = [level_case(rng, level, k) for k in kinds]
+        outs, d = lc.run_transform(emu, nat.COMPRESS, cases, level)
+        back, d2 = pc.run_detransform(emu, nat.COMPRESS, outs, [int(c.size) for c in cases])
+        for i, c in enumerate(cases):
+            if d["status"][i] != 0 or outs[i] != o.zstd_compress_chunk(c.tobytes(), level):
+                bad += 1
+                path = "/tmp/fuzz_bad_level%d_%d_%d.bin" % (level, args.seed, n_cases + i)
+                c.tofile(path)
+                print("MISMATCH level %d seed %d case %d (%s) size %d status %d -> %s" % (level, args.seed, n_cases + i, kinds[i], c.size, d["status"][i], path), file=log, flush=True)
+            if d2["status"][i] != 0 or back[i] != c.tobytes():
+                bad += 1
+                print("DECODE MISMATCH level %d seed %d case %d size %d status %d" % (level, args.seed, n_cases + i, c.size, d2["status"][i]), file=log, flush=True)
+        if batches % 4 == 0:
+            try:
+                lc.check_vs_oracle(emu, o, nat.COMPRESS | nat.ENCRYPT | nat.CRC, cases[:3], level)
+            except AssertionError as e:
+                bad += 1
+                print("CHAIN MISMATCH level %d seed %d case %d: %s" % (level, args.seed, n_cases, e), file=log, flush=True)
+        batches += 1; n_cases += len(cases); n_bytes += sum(int(c.size) for c in cases)
+        if batches % 10 == 0:
+            print("[%6.0fs] level %d seed %d: %d cases, %.1f MB, %d bad" % (time.time() - t0, level, args.seed, n_cases, n_bytes / 1e6, bad), file=log, flush=True)
+    print("DONE level %d seed %d: %d cases, %.1f MB, %d bad" % (level, args.seed, n_cases, n_bytes / 1e6, bad), file=log, flush=True)
 
 
 def fuzz_guests(args, emu, o, rng, log):
