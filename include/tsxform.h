@@ -41,6 +41,12 @@ extern "C" {
 #define TSX_COMPRESS 0x1u /* Zstd frame per chunk   (CompressionChunkEnumeration.java:50-63)      */
 #define TSX_ENCRYPT  0x2u /* IV||C||TAG, AES-256-GCM (EncryptionChunkEnumeration.java:66-84)       */
 #define TSX_CRC      0x4u /* CRC32C of the ORIGINAL chunk bytes, out of band       */
+/* Modifier of TSX_COMPRESS on transform: every frame carries a content checksum (ZSTD_c_checksumFlag: descriptor bit 2, and
+ * behind the last block the low 32 bits of XXH64 of the chunk), byte for byte libzstd's frame with that flag.  Without
+ * TSX_COMPRESS it is TSX_E_INVAL.  Detransform accepts and ignores it: there the FRAME decides - a frame that declares a checksum
+ * is always verified, and a mismatch is TSX_E_BAD_FRAME (zstd-jni: "Restored data doesn't match checksum").
+ * tsx_transformed_bound covers the four bytes. */
+#define TSX_ZSTD_CHECKSUM 0x8u
 
 /* where src/dst live */
 /* host pointers.  The batch is cut into pieces whose H2D copy, kernels and D2H copy overlap: pieces of >= 64 MiB in order on three
@@ -97,7 +103,7 @@ typedef struct tsx_chunk_desc {
 /* Per-batch parameters: one (data key, AAD) pair per segment
  * (AesEncryptionProvider.createDataKeyAndAAD, core/.../security/AesEncryptionProvider.java:52-58). */
 typedef struct tsx_batch_params {
-    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC                                  */
+    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC [| TSX_ZSTD_CHECKSUM]                    */
     uint32_t aad_len;      /* reference: 32                                                         */
     uint8_t  key[32];      /* AES-256 data key (SecretKey.getEncoded())                             */
     uint8_t  aad[64];

@@ -36,6 +36,7 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
     private final SecureRandom random;
     private final int zstdProfile;
     private final int zstdLevel;             // 0: the library default (3)
+    private final boolean zstdChecksum;      // content checksum in every frame
     private final int device;
     private final Integer transformedChunkSize;
     private final ArrayDeque<byte[]> ready = new ArrayDeque<>();
@@ -90,7 +91,24 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
                                         final DataKeyAndAAD keyAndAad, final int batchChunks,
                                         final SecureRandom random, final int zstdProfile, final int segmentHash,
                                         final boolean readAhead, final int zstdLevel) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, readAhead, zstdLevel, false);
+    }
+
+    /**
+     * @param zstdChecksum every frame carries a content checksum (libzstd's ZSTD_c_checksumFlag), plugin configuration key
+     *                     {@code compression.zstd.checksum} (INTEGRATION.md 2), default false: the reference's bytes.  Refused when the
+     *                     chain does not compress.  Every reader of the object - zstd-jni on a CPU broker, the GPU fetch path -
+     *                     verifies it without being told.
+     */
+    public GpuTransformChunkEnumeration(final TransformChunkEnumeration inner, final boolean compress,
+                                        final DataKeyAndAAD keyAndAad, final int batchChunks,
+                                        final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                        final boolean readAhead, final int zstdLevel, final boolean zstdChecksum) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
+        if (zstdChecksum && !compress) {
+            throw new IllegalArgumentException("Zstd checksum needs compression");
+        }
+        this.zstdChecksum = zstdChecksum;
         if (zstdLevel < 0 || zstdLevel > 3) {
             throw new IllegalArgumentException("Zstd level must be 1, 2 or 3 (0: library default), " + zstdLevel + " given");
         }
@@ -188,7 +206,8 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
         if (in.isEmpty()) {
             return out;
         }
-        final int flags = (compress ? TsxNative.COMPRESS : 0) | (keyAndAad != null ? TsxNative.ENCRYPT : 0);
+        final int flags = (compress ? TsxNative.COMPRESS : 0) | (keyAndAad != null ? TsxNative.ENCRYPT : 0)
+            | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0);
         // per-thread, reused, pinned (registered with the device): the compressor waves write every chunk's IV || C || TAG straight into the
         // dst buffer's slots (zero-copy output, DESIGN.md section 1) - a pageable buffer would send the batch through copy engines instead.
         // Footprint per thread: ~2.1 GiB at 256 x 4 MiB (source batch + bound-sized output slots), INTEGRATION.md section 4.

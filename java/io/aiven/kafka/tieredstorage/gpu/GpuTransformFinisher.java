@@ -121,6 +121,7 @@ public class GpuTransformFinisher {
     private final SecureRandom random;
     private final int zstdProfile;
     private final int zstdLevel;             // 0: the library default (3)
+    private final boolean zstdChecksum;      // content checksum in every frame
     private final int device;
     private final boolean readAhead;
     private final Bucket rateLimitingBucket;
@@ -157,7 +158,24 @@ public class GpuTransformFinisher {
                                 final int batchChunks, final SecureRandom random, final int zstdProfile, final int segmentHash,
                                 final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
                                 final boolean readAhead, final int zstdLevel) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, originalFileSize, chunkingEnabled,
+            rateLimitingBucket, readAhead, zstdLevel, false);
+    }
+
+    /**
+     * @param zstdChecksum every frame carries a content checksum (libzstd's ZSTD_c_checksumFlag), plugin configuration key
+     *                     {@code compression.zstd.checksum} (INTEGRATION.md 2), default false: the reference's bytes.  Refused when the
+     *                     chain does not compress.
+     */
+    public GpuTransformFinisher(final TransformChunkEnumeration inner, final boolean compress, final DataKeyAndAAD keyAndAad,
+                                final int batchChunks, final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
+                                final boolean readAhead, final int zstdLevel, final boolean zstdChecksum) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
+        if (zstdChecksum && !compress) {
+            throw new IllegalArgumentException("Zstd checksum needs compression");
+        }
+        this.zstdChecksum = zstdChecksum;
         if (zstdLevel < 0 || zstdLevel > 3) {
             throw new IllegalArgumentException("Zstd level must be 1, 2 or 3 (0: library default), " + zstdLevel + " given");
         }
@@ -199,7 +217,8 @@ public class GpuTransformFinisher {
     }
 
     private int flags() {
-        return (compress ? TsxNative.COMPRESS : 0) | (keyAndAad != null ? TsxNative.ENCRYPT : 0);
+        return (compress ? TsxNative.COMPRESS : 0) | (keyAndAad != null ? TsxNative.ENCRYPT : 0)
+            | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0);
     }
 
     private static long align16(final long v) {

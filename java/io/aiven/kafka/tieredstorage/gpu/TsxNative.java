@@ -10,6 +10,12 @@ public final class TsxNative {
     public static final int COMPRESS = 0x1;
     public static final int ENCRYPT = 0x2;
     public static final int CRC = 0x4;
+    /**
+     * With {@link #COMPRESS} on transform: every frame carries a Zstandard content checksum ({@code compression.zstd.checksum}; libzstd's
+     * ZSTD_c_checksumFlag, byte for byte).  The flags travel through {@link #transformBatch} and its siblings as they are.  Detransform
+     * needs no flag: a frame that declares a checksum is always verified, a mismatch is {@link #E_BAD_FRAME}.
+     */
+    public static final int ZSTD_CHECKSUM = 0x8;
 
     public static final int OK = 0;
     public static final int E_TAG_MISMATCH = -5;

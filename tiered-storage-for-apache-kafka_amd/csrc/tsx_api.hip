@@ -848,6 +848,7 @@ static int run_compress(tsx_run& r) {
         }
         tsx_zseg m; memset(&m, 0, sizeof m);
         m.n = sb.n; m.profile = r.params->zstd_profile; m.level = (r.params->zstd_level == 1 || r.params->zstd_level == 2) ? (uint32_t)r.params->zstd_level : 3u;
+        if (r.flags & TSX_ZSTD_CHECKSUM) m.level |= TSX_ZSEG_CHECKSUM;
         m.src_base = r.d_src; m.descs = (self_status ? c->hd_descs : c->d_descs) + sb.lo; m.mid = c->d_mid + (size_t)sb.lo * c->mid_stride; m.mid_stride = c->mid_stride;
         m.zlen = c->d_zlen + sb.lo; m.status = c->d_status + sb.lo; m.work = (uint8_t*)c->d_zwork + (size_t)sb.lo * tsx_zstd_workspace_bytes(1, 0);
         if (self_status) {
@@ -1210,8 +1211,11 @@ static int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc*
     if (mem_kind != TSX_MEM_HOST && mem_kind != TSX_MEM_DEVICE && mem_kind != TSX_MEM_HOST_PACKED) return TSX_E_INVAL;
     const bool packed = mem_kind == TSX_MEM_HOST_PACKED;
     if (packed && mode != 0) return TSX_E_INVAL;
-    const uint32_t flags = mode == 2 ? TSX_CRC : params->flags;
-    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC)) return TSX_E_INVAL;
+    uint32_t flags = mode == 2 ? TSX_CRC : params->flags;
+    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC | TSX_ZSTD_CHECKSUM)) return TSX_E_INVAL;
+    // the content checksum is the compressor's to write; a decoder verifies whatever frame declares one, asked or not
+    if (mode == 0 && (flags & TSX_ZSTD_CHECKSUM) && !(flags & TSX_COMPRESS)) return TSX_E_INVAL;
+    if (mode != 0) flags &= ~TSX_ZSTD_CHECKSUM;
     if (mode != 2) {
         if (params->aad_len > 64) return TSX_E_INVAL;
         if ((flags & TSX_COMPRESS) && !(params->zstd_level >= 0 && params->zstd_level <= 3)) return TSX_E_UNSUPPORTED;   // 0 = 3 (the library default), 1, 2, 3

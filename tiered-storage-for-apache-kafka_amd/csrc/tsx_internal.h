@@ -70,10 +70,12 @@ struct tsx_chain_fuse {          // stages the compressor wave of chunk i runs i
                                  // before the GCM tail and wipes that copy afterwards (no upload, no device-side wipe: nothing but the launch)
 };
 
+#define TSX_ZSEG_CHECKSUM 0x80000000u
 struct tsx_zseg {                // one caller's batch ("member") in the device's compressor service queue (zstd_service_kernel, tsx_service.hip)
     uint32_t n, profile;         // chunks 0 .. n - 1 of the batch; TSX_ZSTD_PROFILE_*
     uint32_t gen, level;         // generation of this member slot: a ticket that names an older generation is skipped (abandoned member);
-                                 // Zstandard level of the member's frames: 1, 2, or anything else = 3
+                                 // Zstandard level of the member's frames: 1, 2, or anything else = 3; TSX_ZSEG_CHECKSUM on top of it:
+                                 // the member's frames carry a content checksum (TSX_ZSTD_CHECKSUM of its batch)
     const uint8_t* src_base; tsx_chunk_desc* descs; uint8_t* mid; uint64_t mid_stride; uint32_t* zlen; int32_t* status; uint8_t* work;
     tsx_chain_fuse fuse;
     // Per-member completion: a wave that has finished its chunk - frame, GCM tail, descriptor, all released to system scope - counts

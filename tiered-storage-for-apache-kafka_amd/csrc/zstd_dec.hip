@@ -7,7 +7,8 @@
 // treeless) literals, predefined / RLE / FSE / repeat sequence tables, repeat offsets.
 // Errors are per chunk: TSX_E_BAD_SIZE when the frame declares no usable content size (the reference throws
 // "Invalid decompressed size"), TSX_E_DST_TOO_SMALL, TSX_E_BAD_FRAME for anything malformed.  A content
-// checksum, when present, is skipped, not verified (the reference's writer never emits one).
+// checksum, when present, is verified against the restored bytes by the execution wave once the frame is complete
+// (zstd-jni: "Restored data doesn't match checksum"); a mismatch is TSX_E_BAD_FRAME like any other damage.
 //
 // A block goes through three stages, each a serial chain that keeps only a few lanes busy, so the chunk's three
 // waves run them one block apart and meet at one workgroup barrier per block:
@@ -300,6 +301,10 @@ block_end:
         if (role == 0 ? fseDone : role == 1 ? prodDone : frameDone) break;     // a wave that has nothing left to do leaves; the barrier counts live waves
     }
     if (role == 2 && err == TSX_OK && opos != contentSize) err = DERR_FRAME;
+    if (role == 2 && err == TSX_OK && hasChecksum) {                    // (the literal wave has found the four bytes at the frame's end: dec_frame_end)
+        __threadfence_block();
+        if (!dec_checksum_ok(out, opos, dec_checksum_at(src, srcSize - 4), lane)) err = DERR_FRAME;
+    }
 done:
 #ifdef TSX_PROF2
     if (lane == 0 && dprof) {                                           // laps: wave 1 -> 0 (literals), 6 (wait); wave 2 -> 3 (execution), 5 (wait); wave 0 -> 1, 2, 4, 7 (wait)
@@ -357,4 +362,18 @@ uint32_t tsx_launch_zstd_decompress(hipStream_t st, const tsx_zstd_consts* /*d_z
 #endif
                        );
     return 1;
+}
+
+// test hook: XXH64 (seed 0) of len bytes at a device address of any alignment, by one wave as the decoders run it -> *out
+__global__ __launch_bounds__(LANES) void xxh64_probe_kernel(const uint8_t* p, uint32_t len, unsigned long long* out) {
+    const unsigned long long h = xxh64_wave(p, len, threadIdx.x);
+    if (threadIdx.x == 0) *out = h;
+}
+extern "C" int tsx_debug_xxh64(const void* dev_ptr, uint32_t len, unsigned long long* out) {
+    unsigned long long* d = nullptr;
+    if (!out || (len && !dev_ptr) || hipMalloc((void**)&d, sizeof *d) != hipSuccess) return TSX_E_INVAL;
+    hipLaunchKernelGGL(xxh64_probe_kernel, dim3(1), dim3(LANES), 0, (hipStream_t)0, (const uint8_t*)dev_ptr, len, d);
+    const hipError_t e = hipMemcpy(out, d, sizeof *d, hipMemcpyDeviceToHost);
+    hipFree(d);
+    return e == hipSuccess ? TSX_OK : TSX_E_DEVICE;
 }

@@ -1,5 +1,5 @@
 // Per-chunk bookkeeping of the block-parallel frame decoder (zstd_dec_blocks.hip): written by its index kernel, completed by its
-// decode kernel, read by its execute kernel.  Lives in the context's block-mode workspace, one header per chunk, zeroed per call.
+// decode kernel, read by its execute kernel.  Lives in the context's block-mode workspace, one header per chunk, reset by the index kernel.
 #pragma once
 #include <stdint.h>
 
@@ -20,8 +20,10 @@ struct ZbBlock {
 };
 struct ZbChunk {
     uint32_t mode;                               // 1: the block form is decoding this chunk; 0: left to (or handed back to) zstd_decompress_kernel
-    uint32_t nblocks, contentSize, pad;
+    uint32_t nblocks, contentSize;
+    uint32_t emitDone;                           // workgroups of zb_emit_kernel that have written their bytes (counted only when the frame has a checksum)
     uint32_t live[32];                           // jump round r left unresolved words in this chunk (round r + 1 returns at once when not)
+    uint32_t hasCksum, cksum;                    // the frame declares a content checksum / its four bytes
     ZbBlock blk[ZB_MAX_BLOCKS];
 };
 #define ZB_CHUNK_HDR_BYTES ((sizeof(ZbChunk) + 255u) & ~(size_t)255u)

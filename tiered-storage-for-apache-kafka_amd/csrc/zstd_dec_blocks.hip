@@ -20,10 +20,12 @@
 //   zb_jump_kernel     <= log3(size) + 1 passes of pointer jumping (two jumps each, in place: three hops guaranteed) over those words: "where I copy from" becomes "where that copies from"
 //                      until every word is a literal - the execution stage without any order between sequences, blocks or
 //                      workgroups (in-order execution is ONE dependency chain through the whole chunk: see the comment there).
-//   zb_emit_kernel     words -> bytes.
+//   zb_emit_kernel     words -> bytes.  A frame with a content checksum is verified here: the emit workgroups of its chunk count themselves
+//                      when their bytes are out, and the last one hashes the chunk on one wave (xxh64_dev.h) - no launch of its own, nothing
+//                      at all for a frame without a checksum.
 //
 // This form is a fast path, not a second authority: anything it does not like (more than 264 blocks, a chunk above 16 MiB, a
-// malformed frame, an offset out of range, a copy chain that does not end in a literal) clears the chunk's `mode` word and zstd_decompress_kernel - which
+// malformed frame, an offset out of range, a copy chain that does not end in a literal, restored bytes that do not match the frame's checksum) clears the chunk's `mode` word and zstd_decompress_kernel - which
 // is launched behind it with that word as its skip list - decodes the chunk and reports the error code.  Bytes are either final
 // and correct or rewritten by the fallback.  Both forms parse frame bytes through the same helpers (zstd_dec_dev.h, dec_*), so
 // they read every frame alike; this file adds only the limits of its own (ZB_MAX_BLOCKS, ZB_MAX_CHUNK, raw / RLE blocks of at most
@@ -65,6 +67,7 @@ __global__ __launch_bounds__(LANES) void zb_index_kernel(const uint8_t* __restri
     const uint32_t lane = threadIdx.x, chunk = blockIdx.x;
     ZbChunk* const C = (ZbChunk*)(hdrs + (size_t)chunk * ZB_CHUNK_HDR_BYTES);
     if (lane < 32) C->live[lane] = 0;
+    if (lane == 0) { C->emitDone = 0; C->hasCksum = 0; }
     if (lane == 0) C->mode = 0;                                       // "not taken" until the last line of this kernel says otherwise (no memset launch: nothing
                                                                       // else of the header is read before this kernel has written it)
     if (status[chunk] != TSX_OK) return;                              // nothing to decode, nothing to fall back to
@@ -88,6 +91,10 @@ __global__ __launch_bounds__(LANES) void zb_index_kernel(const uint8_t* __restri
                 sOff[n] = bh.off; sSize[n] = bh.bsize; sType[n] = (uint8_t)(bh.btype | (bh.last << 2));
                 n++; p = bh.next;
                 if (bh.last) { closed = dec_frame_end(p, srcSize, fh.hasChecksum); break; }
+            }
+            if (closed && fh.hasChecksum) {
+                if (fh.contentSize == 0) break;                         // no byte, no emit wave to check it: the chunk-serial kernel does
+                C->cksum = dec_checksum_at(src, p); C->hasCksum = 1;
             }
             if (closed) bad = 0;
         } while (0);
@@ -495,18 +502,24 @@ __global__ __launch_bounds__(256) void zb_jump_kernel(uint8_t* __restrict__ hdrs
     }
 }
 
-// words -> bytes; a word that is still a position after the last round means a corrupt chain: the chunk goes back to the fallback
+// words -> bytes; a word that is still a position after the last round means a corrupt chain: the chunk goes back to the fallback.
+// So does a chunk whose bytes do not match its frame's content checksum.  The bytes exist only here, and nothing orders the emit
+// workgroups of a chunk: every workgroup that has written bytes releases them (one device-scope fence behind its barrier) and counts
+// itself in C->emitDone; the first wave of the workgroup that completes the count acquires the others' bytes and hashes the chunk on
+// its own - milliseconds for 4 MiB, which a fetch of checksummed frames pays and any other fetch does not: it leaves
+// before the barrier.
 __global__ __launch_bounds__(256) void zb_emit_kernel(const tsx_chunk_desc* __restrict__ descs, uint8_t* __restrict__ dst_base, uint8_t* __restrict__ hdrs,
                                                       uint8_t* __restrict__ arenas, uint64_t astride, uint32_t lit_cap, uint32_t seq_cap) {
     const uint32_t chunk = blockIdx.y;
     ZbChunk* const C = (ZbChunk*)(hdrs + (size_t)chunk * ZB_CHUNK_HDR_BYTES);
     if (C->mode != 1) return;
-    const uint32_t n = C->contentSize, p = (blockIdx.x * 256 + threadIdx.x) * 16;
-    if (p >= n) return;
+    const uint32_t n = C->contentSize, p = (blockIdx.x * 256 + threadIdx.x) * 16, lane = threadIdx.x & (LANES - 1);
+    if (p - lane * 16 >= n) return;                                     // whole waves leave: the lanes of a wave with bytes stay together for the hand-off below
     const uint32_t* const words = (const uint32_t*)(arenas + (size_t)chunk * astride + lit_cap + 12u * (size_t)seq_cap);
     uint8_t* const out = dst_base + descs[chunk].dst_off;                // slots are 16-byte aligned
     uint32_t all = ZB_LIT;
-    if (p + 16 <= n) {
+    if (p >= n) {}
+    else if (p + 16 <= n) {
         uint32_t w[4];
         for (int k = 0; k < 4; k++) {
             const uint4 v = *reinterpret_cast<const uint4*>(words + p + 4 * k);
@@ -518,6 +531,16 @@ __global__ __launch_bounds__(256) void zb_emit_kernel(const tsx_chunk_desc* __re
         for (uint32_t q = p; q < n; q++) { const uint32_t v = words[q]; all &= v; out[q] = (uint8_t)v; }
     }
     if (!(all & ZB_LIT)) ZB_STORE_AGENT(&C->mode, 0u);
+    if (!DUNI(C->hasCksum)) return;
+    __syncthreads();                                                    // (waves that have left are not waited for) the workgroup's bytes are written ...
+    if (threadIdx.x >= LANES) return;
+    __threadfence();                                                    // ... and released, with its verdict on their words, before its count: one fence per 4 KiB
+    uint32_t last = 0;
+    if (lane == 0) last = atomicAdd(&C->emitDone, 1u) + 1 == (n + 4095) / 4096 ? 1u : 0u;
+    if (!DUNI(last)) return;
+    __threadfence();                                                    // acquire: every counted workgroup's bytes
+    if (DUNI(ZB_LOAD_AGENT(&C->mode)) != 1) return;                     // handed back already
+    if (!dec_checksum_ok(out, n, DUNI(C->cksum), lane) && lane == 0) ZB_STORE_AGENT(&C->mode, 0u);
 }
 
 // ---------------------------------------------------------------------------------------------------

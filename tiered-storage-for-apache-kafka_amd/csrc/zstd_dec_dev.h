@@ -3,7 +3,8 @@
 //   format tables, bit readers, the LDS state of a decoding workgroup (DecLds), FSE / Huffman table builders;
 //   every stage that parses frame bytes, once for both kernels:
 //     dec_frame_header    magic, descriptor, window, dictionary ID, content size
-//     dec_block_header    one block header; dec_frame_end: the checksum and the frame's end behind the last block
+//     dec_block_header    one block header; dec_frame_end: the checksum's place and the frame's end behind the last block;
+//                         dec_checksum_ok: the restored bytes against that checksum (xxh64_dev.h)
 //     dec_lit_header      literals-section header: raw / RLE / Huffman sizes and stream count
 //     dec_huf_streams     the 1 or 4 Huffman streams through per-stream LDS windows
 //     dec_seq_header      sequence count and table modes; dec_seq_table: one table from its description
@@ -14,6 +15,7 @@
 // carries across blocks, the block form's own limits, and what a failure means to each.
 #pragma once
 #include "zstd_common.h"
+#include "xxh64_dev.h"
 
 #define LANES 64
 #define DERR_FRAME TSX_E_BAD_FRAME
@@ -445,10 +447,19 @@ __device__ __forceinline__ static DecBlockHdr dec_block_header(const uint8_t* __
     h.next = h.off + body; h.ok = 1;
     return h;
 }
-// Behind the last block: the optional content checksum (skipped, not verified), then the frame's end.
+// Behind the last block: the optional content checksum (four bytes, verified by dec_checksum_ok once the content is restored),
+// then the frame's end.
 __device__ __forceinline__ static bool dec_frame_end(uint32_t p, uint32_t srcSize, bool hasChecksum) {
     if (hasChecksum) { if (p + 4 > srcSize) return false; p += 4; }
     return p == srcSize;
+}
+// The four checksum bytes at p: the low 32 bits of XXH64 of the content, little endian.
+__device__ __forceinline__ static uint32_t dec_checksum_at(const uint8_t* __restrict__ src, uint32_t p) {
+    return (uint32_t)src[p] | ((uint32_t)src[p + 1] << 8) | ((uint32_t)src[p + 2] << 16) | ((uint32_t)src[p + 3] << 24);
+}
+// Do the restored bytes out[0, n) hash to `expected`?  One wave, every lane with the same arguments; the bytes are visible to it.
+__device__ __forceinline__ static bool dec_checksum_ok(const uint8_t* out, uint32_t n, uint32_t expected, uint32_t lane) {
+    return (uint32_t)xxh64_wave(out, n, lane) == expected;
 }
 
 // Literals-section header of a compressed block -> section size (0 = malformed).  hl = header bytes, csize = Huffman

@@ -36,6 +36,8 @@
 #include "gcm_dev.h"
 #include "crc_dev.h"
 #include "svc_dev.h"
+#define XXH_WAVE_ATTR __attribute__((noinline))     /* out of line, like the other cold stages: the service kernel keeps its registers */
+#include "xxh64_dev.h"
 
 #define LANES 64
 // "this value is the same in every lane": results of out-of-line calls and LDS broadcasts are divergent to the compiler;
@@ -1852,6 +1854,15 @@ __device__ static ZS_NOINLINE void finish_frame(tsx_chunk_desc* __restrict__ des
     if (lane == 0) { descs[chunk].dst_len = flen + 28; if (fuse.self_status) descs[chunk].status = TSX_OK; }
 }
 
+// The content checksum behind the last block (ZSTD_c_checksumFlag): the low 32 bits of XXH64 of the chunk, little endian.  The hash
+// is taken here, at the chunk's end and from its source bytes, by whichever wave finishes the chunk: one that starts a handed-back
+// chunk again gets here on its own.  Returns the frame's new end.
+__device__ static ZS_NOINLINE uint8_t* append_checksum(uint8_t* op, const uint8_t* __restrict__ src, uint32_t srcSize, uint32_t lane) {
+    const uint32_t h = (uint32_t)xxh64_wave(src, srcSize, lane);
+    if (lane == 0) { op[0] = (uint8_t)h; op[1] = (uint8_t)(h >> 8); op[2] = (uint8_t)(h >> 16); op[3] = (uint8_t)(h >> 24); }
+    return op + 4;
+}
+
 // One chunk, start to finish, in the calling wave: CRC32C head, frame, GCM tail (or the copy into the caller's slot), descriptor.
 // Every argument is the same in all lanes (the service kernel hands them over in SGPRs).
 // `hb` (svc_dev.h: what makes this wave give up its CU) is asked before every block; when it says so, true is returned with the chunk
@@ -1859,13 +1870,15 @@ __device__ static ZS_NOINLINE void finish_frame(tsx_chunk_desc* __restrict__ des
 // next time); hash tables, frame and entropy state live in the chunk's own workspace and are set up afresh by whoever starts the chunk again.
 __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint8_t* __restrict__ src_base, tsx_chunk_desc* __restrict__ descs,
                                                            uint8_t* __restrict__ mid, uint64_t mid_stride, uint32_t* __restrict__ zlen,
-                                                           int32_t* __restrict__ status, uint8_t* __restrict__ work, uint32_t profile, uint32_t level, uint32_t sched,
+                                                           int32_t* __restrict__ status, uint8_t* __restrict__ work, uint32_t profile, uint32_t level_word, uint32_t sched,
                                                            const tsx_chain_fuse fuse, const uint32_t chunk, const svc_handback hb
 #ifdef TSX_PROF
                                                            , unsigned long long* __restrict__ prof_out
 #endif
                                                            ) {
     const uint32_t lane = threadIdx.x;
+    const uint32_t level = level_word & ~TSX_ZSEG_CHECKSUM;
+    const bool checksum = (level_word & TSX_ZSEG_CHECKSUM) != 0;
 #ifdef TSX_PROF
     if (lane == 0) { for (int i = 0; i < 24; i++) g_prof[i] = 0; g_prof[22] = g_prof[23] = (unsigned long long)clock64(); g_prof[2] = wall_clock64(); }
     __syncthreads();
@@ -1904,14 +1917,14 @@ __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint
         for (uint32_t i = lane; i < (1u << cp.hashLog) / 4; i += LANES) a[i] = z;
         if (!fast) for (uint32_t i = lane; i < (1u << cp.chainLog) / 4; i += LANES) b[i] = z;
     }
-    // ---- frame header (ZSTD_writeFrameHeader: content size known, no checksum, no dictID) ----
+    // ---- frame header (ZSTD_writeFrameHeader: content size known, the checksum bit on request, no dictID) ----
     uint32_t hdr = 0;
     {   const uint32_t windowSize = 1u << cp.windowLog;
         const uint32_t single = windowSize >= srcSize;
         const uint32_t fcs = (srcSize >= 256) + (srcSize >= 65536 + 256);
         uint8_t h[16]; uint32_t k = 0;
         h[k++] = 0x28; h[k++] = 0xB5; h[k++] = 0x2F; h[k++] = 0xFD;
-        h[k++] = (uint8_t)((single << 5) + (fcs << 6));
+        h[k++] = (uint8_t)((single << 5) + (fcs << 6) + (checksum ? 4u : 0u));
         if (!single) h[k++] = (uint8_t)((cp.windowLog - 10) << 3);
         if (fcs == 0) { if (single) h[k++] = (uint8_t)srcSize; }
         else if (fcs == 1) { h[k++] = (uint8_t)(srcSize - 256); h[k++] = (uint8_t)((srcSize - 256) >> 8); }
@@ -1922,7 +1935,9 @@ __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint
     uint8_t* op = frame + hdr;
     if (srcSize == 0) {
         if (lane == 0) { op[0] = 1; op[1] = 0; op[2] = 0; }
-        finish_frame(descs, chunk, frame, hdr + 3, zlen, status, fuse, ws + ZS_WS_KEYCOPY, L, lane);
+        op += 3;
+        if (checksum) op = append_checksum(op, src, 0, lane);
+        finish_frame(descs, chunk, frame, (uint32_t)(op - frame), zlen, status, fuse, ws + ZS_WS_KEYCOPY, L, lane);
         return false;
     }
     uint32_t* const hufSave = (uint32_t*)(ws + ZS_WS_HUFSAVE);
@@ -2013,8 +2028,13 @@ __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint
         ipos += blockSize; remaining -= blockSize; op += cSize; first = false;
         __syncthreads();
     }
+    if (checksum) {
+        op = append_checksum(op, src, srcSize, lane);
+        __threadfence_block();
+        __syncthreads();
+    }
     finish_frame(descs, chunk, frame, (uint32_t)(op - frame), zlen, status, fuse, ws + ZS_WS_KEYCOPY, L, lane);
-    PT(17);
+    PT(17);                                                             // (with a content checksum: its hash as well)
 #ifdef TSX_PROF
     if (lane == 0 && prof_out) {
         g_prof[14] = (unsigned long long)clock64() - g_prof[22];

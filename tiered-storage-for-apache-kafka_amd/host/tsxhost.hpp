@@ -247,11 +247,14 @@ public:
     GpuTransformChunkEnumeration(std::shared_ptr<Backend> backend, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                  std::optional<DataKeyAndAAD> encryption, IvSupplier ivSupplier = secureRandomIvSupplier(),
                                  int batchChunks = 64, bool withCrc = false, uint32_t zstdProfile = TSX_ZSTD_PROFILE_1_5_7, bool readAhead = true,
-                                 int zstdLevel = 0);
+                                 int zstdLevel = 0, bool zstdChecksum = false);
     ~GpuTransformChunkEnumeration() override;
     // Zstandard level of the frames (compression.zstd.level): 0 = the library default (3, what the reference uses), 1, 2 or 3;
     // anything else is refused here, not at the first batch
     int zstdLevel() const { return level_; }
+    // content checksum in every frame (compression.zstd.checksum, TSX_ZSTD_CHECKSUM): off = the reference's bytes; refused here when
+    // the chain does not compress.  (Every fetch verifies a checksum that is there - the fetch side has no option.)
+    bool zstdChecksum() const { return checksum_; }
     int originalChunkSize() const override { return inner_->originalChunkSize(); }
     std::optional<int> transformedChunkSize() const override { return transformedChunkSize_; }
     bool hasMoreElements() override;
@@ -281,6 +284,7 @@ private:
     uint32_t profile_;
     bool readAhead_;
     int level_;
+    bool checksum_;
     std::optional<int> transformedChunkSize_;
     std::vector<Bytes> ready_;
     size_t next_ = 0;
@@ -329,6 +333,7 @@ public:
     std::shared_ptr<ChunkIndex> chunkIndex();              // "Chunk index was not built, was finisher used?" until the object has been drained
     const std::vector<uint32_t>& crc32cOfOriginalChunks() const { return crcs_; }
     int zstdLevel() const { return inner_->zstdLevel(); }   // the enumeration's (the finisher transforms through it)
+    bool zstdChecksum() const { return inner_->zstdChecksum(); }
 
 private:
     bool nextBatch();

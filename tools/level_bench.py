@@ -4,8 +4,11 @@ in HBM, 4 MiB chunks, CRC32C + Zstd + AES-256-GCM, 5 callers, device-resident ba
 B replicated over the same batch).  The levels run in alternating order (1 2 3, then 3 2 1, ...); for every run: GiB/s of original bytes,
 transformed / original, and the compressor service's kernel time; a sample of every level's timed chunks is checked against libzstd
 (+ the oracle's GCM).  One JSON line per run, then a summary line.
-  python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8]"""
+--checksum: every level runs twice per round, with and without a content checksum in its frames (TSX_ZSTD_CHECKSUM), alternating the same
+way; the frames with one are checked against libzstd's own ZSTD_c_checksumFlag frames.
+  python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8] [--levels 3] [--checksum]"""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--segments", type=int, default=8)
     ap.add_argument("--check", type=int, default=16, help="timed chunks per run checked against libzstd")
     ap.add_argument("--levels", default="1,2,3")
+    ap.add_argument("--checksum", action="store_true", help="each level with and without TSX_ZSTD_CHECKSUM, alternating")
     args = ap.parse_args()
 
     import torch  # before libtsxform: one shared HIP runtime
@@ -48,7 +52,29 @@ def main():
     n = args.segments * cps
     T = args.callers
     flags = nat.COMPRESS | nat.ENCRYPT | nat.CRC
-    levels = [int(x) for x in args.levels.split(",")]
+    levels = [(int(x), ck) for x in args.levels.split(",") for ck in ((False, True) if args.checksum else (False,))]
+
+    def libzstd_frame(raw, level, checksum):
+        """libzstd's frame as oracle/zstd_ref.c makes it, with ZSTD_c_checksumFlag on request."""
+        if not checksum:
+            return o.zstd_compress_chunk(raw, level)
+        Z = ctypes.CDLL(o.lib().orc_zstd_path().decode())
+        Z.ZSTD_createCCtx.restype = ctypes.c_void_p; Z.ZSTD_freeCCtx.argtypes = [ctypes.c_void_p]
+        Z.ZSTD_CCtx_setParameter.restype = ctypes.c_size_t; Z.ZSTD_CCtx_setParameter.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        Z.ZSTD_CCtx_setPledgedSrcSize.restype = ctypes.c_size_t; Z.ZSTD_CCtx_setPledgedSrcSize.argtypes = [ctypes.c_void_p, ctypes.c_ulonglong]
+        Z.ZSTD_compress2.restype = ctypes.c_size_t; Z.ZSTD_compress2.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+        Z.ZSTD_compressBound.restype = ctypes.c_size_t; Z.ZSTD_compressBound.argtypes = [ctypes.c_size_t]
+        Z.ZSTD_isError.restype = ctypes.c_uint; Z.ZSTD_isError.argtypes = [ctypes.c_size_t]
+        a = np.frombuffer(raw, np.uint8)
+        out = np.zeros(Z.ZSTD_compressBound(a.size), np.uint8)
+        c = Z.ZSTD_createCCtx()
+        Z.ZSTD_CCtx_setPledgedSrcSize(c, a.size)
+        for prm, v in ((200, 1), (100, level), (201, 1)):
+            Z.ZSTD_CCtx_setParameter(c, prm, v)
+        r = Z.ZSTD_compress2(c, out.ctypes.data, out.size, a.ctypes.data, a.size)
+        Z.ZSTD_freeCCtx(c)
+        assert not Z.ZSTD_isError(r)
+        return out[:r].tobytes()
     slot = (N.transformed_bound(CH, flags) + 63) // 64 * 64
     src = torch.empty(n * CH, dtype=torch.uint8, device=dev)
     dsts = [torch.empty(n * slot, dtype=torch.uint8, device=dev) for _ in range(T)]
@@ -84,8 +110,8 @@ def main():
         order = []
         for r in range(args.rounds):
             order += levels if r % 2 == 0 else levels[::-1]
-        for level in order:
-            p = nat.Native.make_params(flags, synth.KEY, synth.AAD, zstd_level=level)
+        for level, ck in order:
+            p = nat.Native.make_params(flags | (nat.ZSTD_CHECKSUM if ck else 0), synth.KEY, synth.AAD, zstd_level=level)
             ds = [d.copy() for _ in range(T)]
 
             def step(t):
@@ -115,9 +141,9 @@ def main():
             for i in sample:
                 got = host[i * slot:i * slot + int(ds[0]["dst_len"][i])].cpu().numpy().tobytes()
                 raw = np.ascontiguousarray(host_chunk(i)).tobytes()
-                exp = o.gcm_encrypt_chunk(synth.KEY, ds[0]["iv"][i].tobytes(), synth.AAD, o.zstd_compress_chunk(raw, level))
+                exp = o.gcm_encrypt_chunk(synth.KEY, ds[0]["iv"][i].tobytes(), synth.AAD, libzstd_frame(raw, level, ck))
                 ok = ok and got == exp
-            row = {"content": content, "level": level, "gibs": round(args.steps * n * CH / GiB / el, 3), "elapsed_s": round(el, 3),
+            row = {"content": content, "level": level, "checksum": ck, "gibs": round(args.steps * n * CH / GiB / el, 3), "elapsed_s": round(el, 3),
                    "ratio": round(float(ds[0]["dst_len"].astype(np.int64).sum() - 28 * n) / (n * CH), 4),
                    "kernel_ms": round(s1["kernel_ms"] - s0["kernel_ms"], 1), "launches": s1["launches"] - s0["launches"],
                    "chunks": n, "distinct_chunks": distinct, "steps": args.steps, "callers": T,
@@ -126,10 +152,10 @@ def main():
             print(json.dumps(row), flush=True)
     summary = {}
     for r in rows:
-        k = "%s_L%d" % (r["content"], r["level"])
+        k = "%s_L%d%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else "")
         summary.setdefault(k, []).append(r["gibs"])
     print(json.dumps({"metric": "GiB/s of original bytes per level (runs in order)", "runs": summary,
-                      "ratio": {"%s_L%d" % (r["content"], r["level"]): r["ratio"] for r in rows},
+                      "ratio": {"%s_L%d%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else ""): r["ratio"] for r in rows},
                       "all_exact": all(r["exact_vs_libzstd"] for r in rows), "libzstd": o.zstd_version(), "tsxform": N.version()}), flush=True)
 
 

@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 NAMES = {0: "setup+table zero", 1: "split_block", 2: "match: search steps", 3: "match: extend+store", 4: "match_block (parse of the block, whole)",
          5: "lit: histogram/sample", 6: "lit: lane0 huffman build", 7: "lit: huffman encode", 8: "seq: codes+hist", 9: "seq: lane0 FSE tables",
          10: "seq: lane0 encode", 11: "emit/copy + misc", 12: "#search steps", 13: "#sequences", 14: "total cycles", 15: "sum K (positions evaluated)",
-         16: "CRC32C head", 17: "GCM tail / copy to the slot", 18: "gather literals", 19: "#steps with hash collision (slow path)", 20: "#blocks", 21: "#extension passes from global"}
+         16: "CRC32C head", 17: "content checksum (--checksum) + GCM tail / copy to the slot", 18: "gather literals", 19: "#steps with hash collision (slow path)", 20: "#blocks", 21: "#extension passes from global"}
 
 
 def main():
@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--profile", default="1_5_7", choices=["1_5_7", "1_5_6"], help="Zstd profile (the 1.5.7 pre-splitter on / off)")
     ap.add_argument("--config", default="", help="key=value,... for tsx_debug_config before the batches (e.g. fetch_quiet_ms=2000)")
     ap.add_argument("--where", action="store_true", help="per-chunk wall time by where the chunk ran: guest waves (reserved CUs) against the others")
+    ap.add_argument("--checksum", action="store_true", help="frames with a content checksum (TSX_ZSTD_CHECKSUM): its hash is part of bucket 17")
     ap.add_argument("--lib", default="libtsxform_prof.so", help="libtsxform_prof.so (lap timers) or libtsxform.so (plain, for rocprofv3 runs)")
     args = ap.parse_args()
     import torch
@@ -55,7 +56,7 @@ def main():
     for i in range(uniq, n, uniq):
         m = min(uniq, n - i)
         src[i * CH:(i + m) * CH] = src[:m * CH]
-    flags = (nat.COMPRESS | nat.ENCRYPT | nat.CRC) if args.chain else nat.COMPRESS
+    flags = ((nat.COMPRESS | nat.ENCRYPT | nat.CRC) if args.chain else nat.COMPRESS) | (nat.ZSTD_CHECKSUM if args.checksum else 0)
     slot = (N.transformed_bound(CH, flags) + 63) // 64 * 64
     dst = torch.empty(n * slot, dtype=torch.uint8, device=dev)
     prof = torch.zeros(n * 24, dtype=torch.int64, device=dev)
