@@ -47,6 +47,16 @@ extern "C" {
  * is always verified, and a mismatch is TSX_E_BAD_FRAME (zstd-jni: "Restored data doesn't match checksum").
  * tsx_transformed_bound covers the four bytes. */
 #define TSX_ZSTD_CHECKSUM 0x8u
+/* Modifier of TSX_COMPRESS on transform: verify on upload.  Every Zstandard frame the device has written is read back by the decoder's
+ * own parsing code and compared with the chunk it was written from, before the chunk is reported: a chunk whose frame does not restore
+ * it byte for byte (or whose content checksum is not the chunk's) gets status TSX_E_VERIFY and dst_len 0; the call still returns TSX_OK
+ * and the other chunks are delivered.  With the flag set no chunk is reported TSX_OK unverified (TSX_E_NOMEM when the verifier finds no
+ * memory).  Scope: the Zstandard frame.  The AES-GCM stage behind it is NOT re-checked - its output may already be in the caller's
+ * memory, and a wrong tag is at least detected by every reader.  While verifying uploads run, the compute units reserved for fetches
+ * stay reserved (the verifier's kernels are ordinary kernels: tsx_config.fetch_quiet_ms).  On a verifying transform tsx_timing's
+ * unzstd_ms / unzstd_launches are the verifier's.  Without TSX_COMPRESS it is TSX_E_INVAL; detransform accepts and ignores it
+ * (callers build one flags word for both directions).  (0x10 stays unassigned.) */
+#define TSX_VERIFY 0x20u
 
 /* where src/dst live */
 /* host pointers.  The batch is cut into pieces whose H2D copy, kernels and D2H copy overlap: pieces of >= 64 MiB in order on three
@@ -84,6 +94,7 @@ extern "C" {
                                    "Invalid decompressed size: n" (DecompressionChunkEnumeration.java:42-44) */
 #define TSX_E_SHORT_CHUNK   -8  /* encrypted chunk shorter than IV+TAG                            */
 #define TSX_E_UNSUPPORTED   -9
+#define TSX_E_VERIFY        -10 /* TSX_VERIFY: the frame written for this chunk does not restore it (per chunk)  */
 
 /* Per-chunk descriptor; mirrors io.aiven.kafka.tieredstorage.Chunk (core/.../Chunk.java:21-36:
  * id, originalPosition, originalSize, transformedPosition, transformedSize) with the in/out split
@@ -93,7 +104,9 @@ typedef struct tsx_chunk_desc {
     uint64_t dst_off;  /* in : offset of this chunk's output slot within dst                        */
     uint32_t src_len;  /* in : input bytes (originalSize on transform, transformedSize on detransform) */
     uint32_t dst_cap;  /* in : capacity of the output slot                                          */
-    uint32_t dst_len;  /* out: bytes produced                                                       */
+    uint32_t dst_len;  /* out: bytes produced; 0 when status != TSX_OK - what the chunk's slot (or, packed, the buffer behind
+                               the packed chunks) then holds is undefined: with zero-copy output a failed chunk's bytes
+                               may already have been written there                                          */
     uint32_t crc32c;   /* out: CRC32C of the original (pre-transform / restored) bytes if TSX_CRC   */
     int32_t  status;   /* out: TSX_OK or a TSX_E_* code for this chunk                              */
     uint8_t  iv[12];   /* in : GCM IV for transform (host SecureRandom, AesEncryptionProvider.java:66-71);
@@ -103,7 +116,7 @@ typedef struct tsx_chunk_desc {
 /* Per-batch parameters: one (data key, AAD) pair per segment
  * (AesEncryptionProvider.createDataKeyAndAAD, core/.../security/AesEncryptionProvider.java:52-58). */
 typedef struct tsx_batch_params {
-    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC [| TSX_ZSTD_CHECKSUM]                    */
+    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC [| TSX_ZSTD_CHECKSUM] [| TSX_VERIFY]     */
     uint32_t aad_len;      /* reference: 32                                                         */
     uint8_t  key[32];      /* AES-256 data key (SecretKey.getEncoded())                             */
     uint8_t  aad[64];

@@ -37,6 +37,7 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
     private final int zstdProfile;
     private final int zstdLevel;             // 0: the library default (3)
     private final boolean zstdChecksum;      // content checksum in every frame
+    private final boolean zstdVerify;        // every frame is read back on the device and compared with its chunk
     private final int device;
     private final Integer transformedChunkSize;
     private final ArrayDeque<byte[]> ready = new ArrayDeque<>();
@@ -104,11 +105,31 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
                                         final DataKeyAndAAD keyAndAad, final int batchChunks,
                                         final SecureRandom random, final int zstdProfile, final int segmentHash,
                                         final boolean readAhead, final int zstdLevel, final boolean zstdChecksum) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, readAhead, zstdLevel, zstdChecksum, false);
+    }
+
+    /**
+     * @param zstdVerify verify on upload, plugin configuration key {@code compression.zstd.verify} (INTEGRATION.md 2), default false:
+     *                   every Zstandard frame the device has written is decoded by the decoder's parsing code and compared with its
+     *                   chunk before the chunk is handed on.  A chunk whose frame does not restore it fails the batch
+     *                   ({@link TsxNative#E_VERIFY}, the exception any failed chunk raises): the segment copy fails, the broker
+     *                   retries it and keeps the local segment.  Covers the frame, not the encryption behind it.  Refused when the
+     *                   chain does not compress.
+     */
+    public GpuTransformChunkEnumeration(final TransformChunkEnumeration inner, final boolean compress,
+                                        final DataKeyAndAAD keyAndAad, final int batchChunks,
+                                        final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                        final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
+                                        final boolean zstdVerify) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
         if (zstdChecksum && !compress) {
             throw new IllegalArgumentException("Zstd checksum needs compression");
         }
         this.zstdChecksum = zstdChecksum;
+        if (zstdVerify && !compress) {
+            throw new IllegalArgumentException("Zstd verification needs compression");
+        }
+        this.zstdVerify = zstdVerify;
         if (zstdLevel < 0 || zstdLevel > 3) {
             throw new IllegalArgumentException("Zstd level must be 1, 2 or 3 (0: library default), " + zstdLevel + " given");
         }
@@ -207,7 +228,8 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
             return out;
         }
         final int flags = (compress ? TsxNative.COMPRESS : 0) | (keyAndAad != null ? TsxNative.ENCRYPT : 0)
-            | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0);
+            | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0)
+            | (zstdVerify ? TsxNative.VERIFY : 0);
         // per-thread, reused, pinned (registered with the device): the compressor waves write every chunk's IV || C || TAG straight into the
         // dst buffer's slots (zero-copy output, DESIGN.md section 1) - a pageable buffer would send the batch through copy engines instead.
         // Footprint per thread: ~2.1 GiB at 256 x 4 MiB (source batch + bound-sized output slots), INTEGRATION.md section 4.

@@ -122,6 +122,7 @@ public class GpuTransformFinisher {
     private final int zstdProfile;
     private final int zstdLevel;             // 0: the library default (3)
     private final boolean zstdChecksum;      // content checksum in every frame
+    private final boolean zstdVerify;        // every frame is read back on the device and compared with its chunk
     private final int device;
     private final boolean readAhead;
     private final Bucket rateLimitingBucket;
@@ -171,11 +172,32 @@ public class GpuTransformFinisher {
                                 final int batchChunks, final SecureRandom random, final int zstdProfile, final int segmentHash,
                                 final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
                                 final boolean readAhead, final int zstdLevel, final boolean zstdChecksum) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, originalFileSize, chunkingEnabled,
+            rateLimitingBucket, readAhead, zstdLevel, zstdChecksum, false);
+    }
+
+    /**
+     * @param zstdVerify verify on upload, plugin configuration key {@code compression.zstd.verify} (INTEGRATION.md 2), default false:
+     *                   every Zstandard frame the device has written is decoded by the decoder's parsing code and compared with its
+     *                   chunk before the chunk is handed on.  A chunk whose frame does not restore it fails the batch
+     *                   ({@link TsxNative#E_VERIFY}, the exception any failed chunk raises): the segment copy fails, the broker
+     *                   retries it and keeps the local segment.  Covers the frame, not the encryption behind it.  Refused when the
+     *                   chain does not compress.
+     */
+    public GpuTransformFinisher(final TransformChunkEnumeration inner, final boolean compress, final DataKeyAndAAD keyAndAad,
+                                final int batchChunks, final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
+                                final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
+                                final boolean zstdVerify) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
         if (zstdChecksum && !compress) {
             throw new IllegalArgumentException("Zstd checksum needs compression");
         }
         this.zstdChecksum = zstdChecksum;
+        if (zstdVerify && !compress) {
+            throw new IllegalArgumentException("Zstd verification needs compression");
+        }
+        this.zstdVerify = zstdVerify;
         if (zstdLevel < 0 || zstdLevel > 3) {
             throw new IllegalArgumentException("Zstd level must be 1, 2 or 3 (0: library default), " + zstdLevel + " given");
         }
@@ -218,7 +240,8 @@ public class GpuTransformFinisher {
 
     private int flags() {
         return (compress ? TsxNative.COMPRESS : 0) | (keyAndAad != null ? TsxNative.ENCRYPT : 0)
-            | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0);
+            | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0)
+            | (zstdVerify ? TsxNative.VERIFY : 0);
     }
 
     private static long align16(final long v) {

@@ -16,11 +16,19 @@ public final class TsxNative {
      * needs no flag: a frame that declares a checksum is always verified, a mismatch is {@link #E_BAD_FRAME}.
      */
     public static final int ZSTD_CHECKSUM = 0x8;
+    /**
+     * With {@link #COMPRESS} on transform: verify on upload ({@code compression.zstd.verify}).  Every frame the device has written is read
+     * back and compared with its chunk before the chunk is reported; a chunk whose frame does not restore it has status
+     * {@link #E_VERIFY}.  Detransform accepts and ignores the flag.
+     */
+    public static final int VERIFY = 0x20;
 
     public static final int OK = 0;
     public static final int E_TAG_MISMATCH = -5;
     public static final int E_BAD_FRAME = -6;
     public static final int E_BAD_SIZE = -7;
+    /** Under {@link #VERIFY}: the frame written for this chunk does not restore it (per chunk; the batch call itself succeeds). */
+    public static final int E_VERIFY = -10;
 
     /** Size of one tsx_chunk_desc (include/tsxform.h), written/read through a direct little-endian ByteBuffer. */
     public static final int DESC_BYTES = 48;

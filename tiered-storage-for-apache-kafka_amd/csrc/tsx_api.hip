@@ -14,6 +14,7 @@
 
 #include "tsx_host.h"
 #include "tsx_service.h"
+#include "zstd_dec_blocks.h"
 
 tsx_cfg g_cfg;
 
@@ -44,6 +45,8 @@ extern "C" long long tsx_debug_config(const char* key, long long value) {
     CFG_FIELD(zstd_sched, uint32_t) CFG_FIELD(dec_block_chunks, uint32_t) CFG_FIELD(comp_pieces, uint32_t) CFG_FIELD(sub_bytes, long long)
     CFG_FIELD(stages_separate, bool) CFG_FIELD(no_pipeline, bool) CFG_FIELD(no_zero_copy_out, bool) CFG_FIELD(zero_copy_packed, bool)
     CFG_FIELD(gcm_setup_kernel, bool) CFG_FIELD(no_dec_pieces, bool) CFG_FIELD(debug, bool) CFG_FIELD(svc_normal_priority, bool) CFG_FIELD(svc_keep_waves, uint32_t) CFG_FIELD(fetch_quiet_ms, uint32_t) CFG_FIELD(trace, bool)
+    CFG_FIELD(verify_damage_src_chunk, long long) CFG_FIELD(verify_damage_src_off, long long) CFG_FIELD(verify_damage_frame_chunk, long long)
+    CFG_FIELD(verify_damage_frame_off, long long) CFG_FIELD(verify_slice_chunks, uint32_t) CFG_FIELD(verify_force_fallback, bool)
 #undef CFG_FIELD
     return TSX_E_INVAL;
 }
@@ -99,7 +102,20 @@ struct tsx_ctx {
     uint32_t last_members = 0;                     // members the last compressing batch went as (test hook)
     bool last_zero_copy = false;                   // ... and whether its waves wrote into the caller's buffer (test hook)
     bool key_wiped = false;                        // the batch's own wipe_key_kernel has cleared d_key / d_keyraw
+    // verify on upload (TSX_VERIFY): the verifier's words per chunk of a slice, pinned, and as the device addresses them (created by the first verifying batch)
+    uint32_t* h_verdicts = nullptr; uint32_t* hd_verdicts = nullptr; size_t verdicts_cap = 0;
+    uint32_t verify_block_form = 0, verify_fallback = 0;   // chunks of the last batch the block form judged / that were decoded in full (test hook)
 };
+
+// Verify on upload: ONE workspace per device (the literal and sequence arenas are ~21 MiB per 4 MiB chunk: too much per context with 32
+// callers in flight), created by the first verifying batch; a caller holds `mu` while a slice of its piece is verified in it.
+struct tsx_verifier {
+    std::mutex mu;
+    uint8_t* work = nullptr; size_t work_cap = 0;  // [slice descriptors and status words][chunk headers][arenas]
+    uint8_t* full = nullptr; size_t full_cap = 0;  // phase two: a chunk the block form did not take, restored in full
+};
+#define TSX_VERIFY_SLICE_BYTES ((size_t)3 << 29)   /* workspace budget of a slice: 1.5 GiB, ~73 chunks of 4 MiB (at least one chunk whatever its size) */
+#define TSX_V_WANTED 3                             /* fourth word of a chunk's verdict (zstd_dec_blocks.h): the chunk was TSX_OK and is to be verified */
 
 static std::mutex g_mu;
 static std::vector<tsx_device> g_devs;
@@ -136,6 +152,7 @@ extern "C" const char* tsx_strerror(int code) {
         case TSX_E_BAD_SIZE: return "Invalid decompressed size";                           // DecompressionChunkEnumeration.java:43
         case TSX_E_SHORT_CHUNK: return "encrypted chunk shorter than IV + tag";
         case TSX_E_UNSUPPORTED: return "unsupported parameter";
+        case TSX_E_VERIFY: return "the frame written for this chunk does not restore it";
         default: return "unknown error";
     }
 }
@@ -165,6 +182,7 @@ static void device_free_consts(tsx_device& d) {
     svc_destroy(d);
     for (auto& b : d.spare_bwork) (void)hipFree(b.first);
     d.spare_bwork.clear();
+    if (d.verifier) { (void)hipFree(d.verifier->work); (void)hipFree(d.verifier->full); delete d.verifier; d.verifier = nullptr; }
     if (d.copy_in) hipStreamDestroy(d.copy_in);
     if (d.copy_out) hipStreamDestroy(d.copy_out);
     if (d.d_crc) hipFree(d.d_crc);
@@ -278,6 +296,7 @@ static void ctx_free_device_mem(tsx_ctx* c) {
     for (void* p : ptrs) svc_free_dev(c->dev, p);
     svc_free_host(c->dev, c->h_segflag);
     svc_free_host(c->dev, c->h_descs);
+    svc_free_host(c->dev, c->h_verdicts);
     if (c->h_keyraw) { memset(c->h_keyraw, 0, 128); svc_free_host(c->dev, c->h_keyraw); }
     if (c->h_key) { memset(c->h_key, 0, sizeof(tsx_gcm_key)); svc_free_host(c->dev, c->h_key); }
     for (auto& e : c->ev) if (e) hipEventDestroy(e);
@@ -742,6 +761,133 @@ static uint8_t* device_alias_of_range(void* p, size_t bytes) {
 
 static int copy_back(const tsx_run& r, const tsx_sub& sb, size_t* packed_at, bool* packed_full, hipStream_t out_st);
 
+// ---- verify on upload (TSX_VERIFY) -------------------------------------------------------------------------------------------------
+// What the verifier's kernels read, written on the device (the frame sizes exist only there): for chunk i of a slice, vdescs[i] describes
+// its frame to the block form's kernels (zstd_gpu.h: tsx_launch_zstd_verify_blocks), fdescs[i] to the chunk-serial decoder of phase two
+// (output at offset 0 of the verifier's buffer).  status == nullptr: the compressor waves own the status, in the descriptor itself.
+// no_blocks (test hook verify_force_fallback): the block form is told to leave every chunk alone.
+__global__ void verify_plan_kernel(const tsx_chunk_desc* __restrict__ descs, const int32_t* __restrict__ status, const uint32_t* __restrict__ zlen, uint32_t n,
+                                   tsx_chunk_desc* __restrict__ vdescs, tsx_chunk_desc* __restrict__ fdescs, int32_t* __restrict__ vstatus, int32_t* __restrict__ fstatus,
+                                   uint32_t* __restrict__ verdicts, int no_blocks) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const tsx_chunk_desc d = descs[i];
+    const bool wanted = (status ? status[i] : d.status) == TSX_OK;
+    tsx_chunk_desc v = d;
+    v.src_off = 0; v.src_len = zlen[i] + 28; v.dst_cap = d.src_len; v.dst_len = 0; v.status = TSX_OK;
+    v.dst_off = 0; fdescs[i] = v;
+    v.dst_off = d.src_off; vdescs[i] = v;
+    vstatus[i] = wanted && !no_blocks ? TSX_OK : TSX_E_INVAL;
+    fstatus[i] = TSX_OK;
+    verdicts[(size_t)i * ZB_VERDICT_WORDS + TSX_V_WANTED] = wanted ? 1u : 0u;
+}
+static_assert(ZB_VERDICT_WORDS == 4 && TSX_V_WANTED == 3, "a chunk's verdict: the verify kernel's three words and the plan kernel's");
+
+// test hooks verify_damage_*: one byte, one thread
+__global__ void verify_damage_kernel(uint8_t* p) { *p ^= 1; }
+
+// Phase two: the chunk restored in full by the chunk-serial decoder against its source.  V: the chunk's verdict words, zero on entry.
+__global__ __launch_bounds__(256) void verify_compare_kernel(const uint8_t* __restrict__ restored, const uint8_t* __restrict__ orig, const tsx_chunk_desc* __restrict__ fdesc,
+                                                             const int32_t* __restrict__ fstatus, uint32_t* __restrict__ V) {
+    const uint32_t len = fdesc->dst_cap;
+    bool diff = *fstatus != TSX_OK || fdesc->dst_len != len;          // (a frame the decoder rejects, or one of another size, restores nothing)
+    if (!diff) for (uint32_t p = blockIdx.x * 256 + threadIdx.x; p < len; p += gridDim.x * 256) diff |= restored[p] != orig[p];
+    if (diff) V[ZB_V_FAIL] = 1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) V[ZB_V_SEEN] = 1;
+}
+
+static tsx_verifier* verifier_of(tsx_device* dev) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!dev->verifier) dev->verifier = new (std::nothrow) tsx_verifier;
+    return dev->verifier;
+}
+
+// Chunks [sb.lo, sb.lo + sb.n) - a member that has just completed - before anything of them is reported: vcode[i] = 0 (the frame restores
+// the chunk, or the chunk was not TSX_OK anyway), TSX_E_VERIFY, or TSX_E_NOMEM (never "not looked at").  The kernels are ordinary kernels
+// on a chip that compressor waves fill: the piece claims the reserved CUs like a fetch and waits with the fetch side's safety net.
+static int verify_piece(tsx_run& r, const tsx_sub& sb, bool self_status, int32_t* vcode) {
+    tsx_ctx* c = r.c;
+    tsx_device* dev = c->dev;
+    tsx_timing& t = c->timing;
+    for (uint32_t i = 0; i < sb.n; i++) vcode[sb.lo + i] = TSX_E_NOMEM;
+    tsx_verifier* const V = verifier_of(dev);
+    if (!V) return TSX_OK;
+    uint32_t max_len = 0;
+    for (uint32_t i = sb.lo; i < sb.lo + sb.n; i++) if (r.descs[i].src_len > max_len) max_len = r.descs[i].src_len;
+    const size_t per_chunk = tsx_zstd_verify_bytes(1, max_len) + 2 * sizeof(tsx_chunk_desc) + 8;
+    uint32_t slice = g_cfg.verify_slice_chunks ? g_cfg.verify_slice_chunks : (uint32_t)std::min<size_t>(TSX_VERIFY_SLICE_BYTES / per_chunk, sb.n);
+    if (slice < 1) slice = 1;
+    if (slice > sb.n) slice = sb.n;
+    if (c->verdicts_cap < slice) {
+        svc_free_host(dev, c->h_verdicts); c->h_verdicts = nullptr; c->hd_verdicts = nullptr; c->verdicts_cap = 0;
+        const size_t cap = (size_t)slice + slice / 4 + 16;
+        if (hipHostMalloc((void**)&c->h_verdicts, cap * ZB_VERDICT_WORDS * 4, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); c->h_verdicts = nullptr; return TSX_OK; }
+        HIPCHK(hipHostGetDevicePointer((void**)&c->hd_verdicts, c->h_verdicts, 0));
+        c->verdicts_cap = cap;
+    }
+    struct fg_piece {
+        tsx_device* d;
+        explicit fg_piece(tsx_device* dev_) : d(dev_) { svc_foreground_begin(d); }
+        ~fg_piece() { svc_foreground_end(d); }
+    } fg(dev);
+    std::lock_guard<std::mutex> lk(V->mu);
+    const size_t head = ((size_t)slice * (2 * sizeof(tsx_chunk_desc) + 8) + 255) & ~(size_t)255;
+    if (grow(dev, &V->work, &V->work_cap, head + tsx_zstd_verify_bytes(slice, max_len))) { (void)hipGetLastError(); return TSX_OK; }   // every chunk of the piece: TSX_E_NOMEM
+    const long long dsrc = g_cfg.verify_damage_src_chunk, dfrm = g_cfg.verify_damage_frame_chunk;
+    for (uint32_t lo = sb.lo; lo < sb.lo + sb.n; lo += slice) {
+        const uint32_t n = std::min(slice, sb.lo + sb.n - lo);
+        tsx_chunk_desc* const vdescs = (tsx_chunk_desc*)V->work; tsx_chunk_desc* const fdescs = vdescs + slice;
+        int32_t* const vstatus = (int32_t*)(fdescs + slice); int32_t* const fstatus = vstatus + slice;
+        const uint8_t* const frames = c->d_mid + (size_t)lo * c->mid_stride;
+        uint8_t* src_hit = nullptr;
+        memset(c->h_verdicts, 0, (size_t)n * ZB_VERDICT_WORDS * 4);
+        HIPCHK(hipEventRecord(c->ev[0], c->st));
+        if (dsrc >= lo && dsrc < lo + n && g_cfg.verify_damage_src_off >= 0 && g_cfg.verify_damage_src_off < (long long)r.descs[dsrc].src_len) {
+            src_hit = (uint8_t*)r.d_src + r.descs[dsrc].src_off + g_cfg.verify_damage_src_off;
+            hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, c->st, src_hit); t.unzstd_launches++;
+        }
+        if (dfrm >= lo && dfrm < lo + n && g_cfg.verify_damage_frame_off >= 0 && g_cfg.verify_damage_frame_off < (long long)c->mid_stride) {
+            hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, c->st, c->d_mid + (size_t)dfrm * c->mid_stride + g_cfg.verify_damage_frame_off); t.unzstd_launches++;
+        }
+        hipLaunchKernelGGL(verify_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, c->st, (const tsx_chunk_desc*)((self_status ? c->hd_descs : c->d_descs) + lo),
+                           self_status ? (const int32_t*)nullptr : (const int32_t*)(c->d_status + lo), (const uint32_t*)(c->d_zlen + lo), n, vdescs, fdescs, vstatus, fstatus,
+                           c->hd_verdicts, g_cfg.verify_force_fallback ? 1 : 0);
+        t.unzstd_launches += 1 + tsx_launch_zstd_verify_blocks(c->st, frames, (uint64_t)c->mid_stride, vdescs, vstatus, n, max_len, r.d_src, V->work + head, c->hd_verdicts);
+        HIPCHK(hipEventRecord(c->ev[1], c->st));
+        HIPCHK(wait_event_watching(c, c->ev[1]));
+        t.unzstd_ms += ev_ms(c->ev[0], c->ev[1]);
+        // ---- phase two: what the block form did not take (above 16 MiB, more than 264 blocks, a frame it does not parse) is decoded in
+        // full, chunk by chunk, by the register-only build of the chunk-serial decoder (uploads are running: nothing here may need
+        // scratch), and compared byte for byte.  Rare, and allowed to synchronise.
+        for (uint32_t i = 0; i < n; i++) {
+            uint32_t* const W = c->h_verdicts + (size_t)i * ZB_VERDICT_WORDS;
+            const uint32_t j = lo + i;
+            if (!W[TSX_V_WANTED]) { vcode[j] = TSX_OK; continue; }
+            if (W[ZB_V_FAIL]) { vcode[j] = TSX_E_VERIFY; c->verify_block_form++; continue; }
+            if (W[ZB_V_SEEN] && !W[ZB_V_NOT_TAKEN]) { vcode[j] = TSX_OK; c->verify_block_form++; continue; }
+            c->verify_fallback++;
+            uint8_t* fp = V->full;
+            const int grc = grow(dev, &fp, &V->full_cap, (size_t)r.descs[j].src_len + 64);
+            V->full = fp;
+            if (grc) { (void)hipGetLastError(); continue; }            // vcode[j] stays TSX_E_NOMEM
+            W[ZB_V_FAIL] = 0; W[ZB_V_NOT_TAKEN] = 0; W[ZB_V_SEEN] = 0;
+            HIPCHK(hipEventRecord(c->ev[0], c->st));
+            t.unzstd_launches += 1 + tsx_launch_zstd_decompress(c->st, dev->d_zc, c->d_mid + (size_t)j * c->mid_stride, 1, (uint64_t)c->mid_stride, fdescs + i, 1, V->full, fstatus + i,
+                                                                (uint8_t*)c->d_zwork + (size_t)j * tsx_zstd_workspace_bytes(1, 0), nullptr, 0, true);
+            const uint32_t blocks = std::max(1u, std::min(1024u, r.descs[j].src_len / 4096u));
+            hipLaunchKernelGGL(verify_compare_kernel, dim3(blocks), dim3(256), 0, c->st, (const uint8_t*)V->full, r.d_src + r.descs[j].src_off, (const tsx_chunk_desc*)(fdescs + i),
+                               (const int32_t*)(fstatus + i), c->hd_verdicts + (size_t)i * ZB_VERDICT_WORDS);
+            HIPCHK(hipEventRecord(c->ev[1], c->st));
+            HIPCHK(wait_event_watching(c, c->ev[1]));
+            t.unzstd_ms += ev_ms(c->ev[0], c->ev[1]);
+            vcode[j] = W[ZB_V_FAIL] || !W[ZB_V_SEEN] ? TSX_E_VERIFY : TSX_OK;
+        }
+        if (src_hit) { hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, c->st, src_hit); HIPCHK(hipStreamSynchronize(c->st)); }
+    }
+    HIPCHK(hipGetLastError());
+    return TSX_OK;
+}
+
 // ---- the compressing forward chain: members of the device's service ---------------------------------------------------------------------
 // Any compressing batch - explicit context or pooled, device or host memory - takes this way.  The batch is cut into at most comp_pieces
 // members when its input comes from host memory (piece k + 1's input copy overlaps piece k's waves; a member is published when ITS input
@@ -782,6 +928,9 @@ static int run_compress(tsx_run& r) {
     memset(&c->timing, 0, sizeof c->timing);
     tsx_timing& t = c->timing;
     c->last_zero_copy = zc_dst != nullptr;
+    c->verify_block_form = 0; c->verify_fallback = 0;
+    std::vector<int32_t> vcode;                                         // TSX_VERIFY: per chunk, what the verifier has to say (0: nothing)
+    if (r.flags & TSX_VERIFY) vcode.assign(n, 0);
     // ---- the pieces ----
     std::vector<tsx_sub> subs;
     {
@@ -872,6 +1021,8 @@ static int run_compress(tsx_run& r) {
         svc_retire(dev, ids[k], false);
         ids[k] = 0;
         if (k + 1 == ns) t.zstd_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_pub).count();
+        // verify on upload: the piece's frames and their source chunks are both still on the device; the later pieces keep compressing
+        if (!vcode.empty() && (rc = verify_piece(r, sb, self_status, vcode.data()))) return abandon_all(rc);
         if (!self_status) {
             // stages_separate: the frames are in the staging buffer; GCM (or the copy into the slots) and the status publication follow
             tsx_chunk_desc* dd = c->d_descs + sb.lo; int32_t* ds = c->d_status + sb.lo; uint32_t* dz = c->d_zlen + sb.lo;
@@ -893,6 +1044,7 @@ static int run_compress(tsx_run& r) {
             HIPCHK_AB(hipMemcpyAsync(c->h_descs + sb.lo, dd, (size_t)sb.n * sizeof(tsx_chunk_desc), hipMemcpyDeviceToHost, c->st));
             if (hipStreamSynchronize(c->st) != hipSuccess) return abandon_all(TSX_E_DEVICE);
         }
+        if (!vcode.empty()) for (uint32_t i = sb.lo; i < sb.lo + sb.n; i++) if (vcode[i] && c->h_descs[i].status == TSX_OK) { c->h_descs[i].status = vcode[i]; c->h_descs[i].dst_len = 0; }
         memcpy(r.descs + sb.lo, c->h_descs + sb.lo, (size_t)sb.n * sizeof(tsx_chunk_desc));
         if (zc_dst) {                                                   // the bytes are where they belong; a packed batch is packed down in place
             if (r.packed) for (uint32_t i = sb.lo; i < sb.lo + sb.n; i++) {
@@ -1212,10 +1364,11 @@ static int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc*
     const bool packed = mem_kind == TSX_MEM_HOST_PACKED;
     if (packed && mode != 0) return TSX_E_INVAL;
     uint32_t flags = mode == 2 ? TSX_CRC : params->flags;
-    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC | TSX_ZSTD_CHECKSUM)) return TSX_E_INVAL;
-    // the content checksum is the compressor's to write; a decoder verifies whatever frame declares one, asked or not
-    if (mode == 0 && (flags & TSX_ZSTD_CHECKSUM) && !(flags & TSX_COMPRESS)) return TSX_E_INVAL;
-    if (mode != 0) flags &= ~TSX_ZSTD_CHECKSUM;
+    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC | TSX_ZSTD_CHECKSUM | TSX_VERIFY)) return TSX_E_INVAL;
+    // the content checksum is the compressor's to write; a decoder verifies whatever frame declares one, asked or not.  Verify on upload
+    // reads back what the compressor wrote: both modify TSX_COMPRESS on transform and mean nothing anywhere else
+    if (mode == 0 && (flags & (TSX_ZSTD_CHECKSUM | TSX_VERIFY)) && !(flags & TSX_COMPRESS)) return TSX_E_INVAL;
+    if (mode != 0) flags &= ~(TSX_ZSTD_CHECKSUM | TSX_VERIFY);
     if (mode != 2) {
         if (params->aad_len > 64) return TSX_E_INVAL;
         if ((flags & TSX_COMPRESS) && !(params->zstd_level >= 0 && params->zstd_level <= 3)) return TSX_E_UNSUPPORTED;   // 0 = 3 (the library default), 1, 2, 3
@@ -1307,6 +1460,14 @@ extern "C" int tsx_debug_key_residue(tsx_ctx* c) {
 // Test hooks (not part of the ABI): members the context's last compressing batch went as; whether its waves wrote into the caller's buffer.
 extern "C" int tsx_debug_last_members(tsx_ctx* c) { return c ? (int)c->last_members : TSX_E_INVAL; }
 extern "C" int tsx_debug_last_zero_copy(tsx_ctx* c) { return c ? (int)c->last_zero_copy : TSX_E_INVAL; }
+// Test hook (not part of the ABI): which way the chunks of the context's last verifying batch were verified - judged by the block form
+// (passed or failed there), or decoded in full (phase two)
+extern "C" int tsx_debug_verify_counts(tsx_ctx* c, uint32_t* block_form, uint32_t* fallback) {
+    if (!c) return TSX_E_INVAL;
+    if (block_form) *block_form = c->verify_block_form;
+    if (fallback) *fallback = c->verify_fallback;
+    return TSX_OK;
+}
 
 // Test hook (not part of the ABI): how many of the first n chunks of the context's LAST detransform batch were decoded by the
 // block-parallel form (the rest went through the chunk-serial kernel); -1 when that batch did not use the form at all.

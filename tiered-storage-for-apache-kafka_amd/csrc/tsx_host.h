@@ -38,6 +38,11 @@ struct tsx_cfg {
     bool no_dec_pieces = false;           // block-form fetches in one piece
     bool svc_normal_priority = false;     // the service's stream like any other (default: the device's LOWEST stream priority, a hardware queue of its own pool)
     bool trace = false;                   // timestamps of a batch's phases on stderr (tools/fetch_block_probe.py)
+    // verify on upload (TSX_VERIFY): XOR 1 into byte `off` of chunk `chunk` of the batch (-1: none) - of the device copy of its source (put back
+    // behind the verification), of its frame in the staging buffer - after the chunk's member has completed and before it is verified
+    long long verify_damage_src_chunk = -1, verify_damage_src_off = 0, verify_damage_frame_chunk = -1, verify_damage_frame_off = 0;
+    uint32_t verify_slice_chunks = 0;     // chunks per slice of the verifier's workspace (0 = as many as fit its byte budget)
+    bool verify_force_fallback = false;   // every chunk is decoded in full and compared (phase two), none by the block form
 };
 extern tsx_cfg g_cfg;
 
@@ -52,6 +57,7 @@ struct tsx_device_scope {
 };
 
 struct tsx_ctx;
+struct tsx_verifier;                                         // tsx_api.hip: the device's verify-on-upload workspace
 struct tsx_service;                                          // tsx_service.hip: nobody else looks inside
 struct tsx_service_delete { void operator()(tsx_service* s) const; };
 
@@ -71,6 +77,7 @@ struct tsx_device {
     size_t idle_cap = 0;                                     // most idle workspace kept (init_devices: a fraction of THIS device's memory)
     std::vector<std::pair<void*, size_t>> spare_bwork;       // block-form decoder workspaces that left their context (pool_release), for the next one
     std::unique_ptr<tsx_service, tsx_service_delete> svc;
+    tsx_verifier* verifier = nullptr;                        // created by the first verifying batch (under g_mu), freed with the device
     // copy streams of the context-less compressing calls, shared by the callers: ONE of each.  With a stream per caller a segment's copies
     // stood behind other callers' in the engines' queues anyway, and more streams measured worse (profiles/r04_broker_shape_experiments.txt).
     hipStream_t copy_in = nullptr, copy_out = nullptr;

@@ -27,3 +27,9 @@ struct ZbChunk {
     ZbBlock blk[ZB_MAX_BLOCKS];
 };
 #define ZB_CHUNK_HDR_BYTES ((sizeof(ZbChunk) + 255u) & ~(size_t)255u)
+
+// zb_verify_kernel's words per chunk (zero before the launch): see the kernel
+#define ZB_VERDICT_WORDS 4u
+#define ZB_V_FAIL 0
+#define ZB_V_NOT_TAKEN 1
+#define ZB_V_SEEN 2

@@ -458,6 +458,183 @@ __global__ __launch_bounds__(ZB_SC_WAVES * LANES) void zb_scatter_kernel(const u
     if (tid == 0 && sFail) ZB_STORE_AGENT(&C->mode, 0u);                // the chunk-serial kernel behind this launch redoes the chunk
 }
 
+// ---------------------------------------------------------------------------------------------------
+// verify on upload: a frame the compressor has just written, against the chunk it was written from
+//
+// When the expected output is known, nothing has to be executed: the frame restores orig[0, n) exactly if its content size is n and,
+// for every output position p, a literal byte equals orig[p] and a match byte satisfies orig[p - offset] == orig[p] - by induction
+// on p (the bytes before p are orig's, so the byte a match copies IS orig[p - offset]) that is byte equality of the restored chunk.
+// No order between sequences, blocks or workgroups, no word per output byte, no jump passes, no emit: this kernel runs behind
+// zb_index_kernel and zb_decode_kernel in place of zb_scatter_kernel, with that kernel's geometry and its prologue (kept as a copy of
+// its own: the fetch path's kernels stay the code they were) - and where scatter stores words[p], it compares.
+//
+// descs[i] describes FRAME i to the two kernels in front (src_len = frame bytes + 28, read with from_mid = 1; dst_cap = the source
+// chunk's length) and says where the source chunk is: src_base + dst_off.  status[i] != 0: chunk i is not verified.
+// verdicts: ZB_VERDICT_WORDS words per chunk, zero before the launch, in memory the host reads (plain stores; every writer of a word
+// stores the same value):
+//   [ZB_V_FAIL]      the frame does not restore the chunk: a byte differs, an offset reaches before the chunk's first byte, the
+//                    content size is not the chunk's length, or the content checksum is not the SOURCE chunk's
+//   [ZB_V_NOT_TAKEN] the block form has no opinion (its own limits, or a frame it does not parse): the caller decodes the frame in full
+//   [ZB_V_SEEN]      the workgroup of block 0 got past the prologue: without it (and without the other two) nothing looked at the chunk
+// A frame of an EMPTY chunk with a content checksum is one the index kernel leaves to the chunk-serial form (no emit wave would check
+// it); there is no byte to compare, so the first wave checks here that the frame regenerates nothing and carries the empty input's hash.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(ZB_SC_WAVES * LANES) void zb_verify_kernel(const uint8_t* __restrict__ frames, uint64_t mid_stride,
+                                                                        const tsx_chunk_desc* __restrict__ descs, const int32_t* __restrict__ status,
+                                                                        const uint8_t* __restrict__ src_base, uint8_t* __restrict__ hdrs, uint8_t* __restrict__ arenas,
+                                                                        uint64_t astride, uint32_t lit_cap, uint32_t seq_cap, uint32_t* __restrict__ verdicts) {
+    __shared__ uint32_t sRegen[ZB_MAX_BLOCKS];
+    __shared__ uint32_t sHist[3][ZB_MAX_BLOCKS];
+    __shared__ uint8_t sFlag[ZB_MAX_BLOCKS];
+    __shared__ uint32_t sLit[ZB_SC_GROUPS + 1], sTot[ZB_SC_GROUPS + 1];
+    __shared__ uint32_t gStart[ZB_SC_WAVES][LANES + 1], gLL[ZB_SC_WAVES][LANES], gLit[ZB_SC_WAVES][LANES], gSrc[ZB_SC_WAVES][LANES];
+    const uint32_t tid = threadIdx.x, lane = tid & (LANES - 1), wv = DUNI(tid >> 6), b = blockIdx.x, chunk = blockIdx.y;
+    if (status[chunk] != TSX_OK) return;
+    ZbChunk* const C = (ZbChunk*)(hdrs + (size_t)chunk * ZB_CHUNK_HDR_BYTES);
+    uint32_t* const V = verdicts + (size_t)chunk * ZB_VERDICT_WORDS;
+    const tsx_chunk_desc d = descs[chunk];
+    const uint8_t* __restrict__ src = frames + (uint64_t)chunk * mid_stride;
+    const uint8_t* __restrict__ orig = src_base + d.dst_off;
+    const uint32_t origLen = d.dst_cap;
+#define ZV_FAIL() do { if (lane == 0) V[ZB_V_FAIL] = 1; } while (0)
+#define ZV_NOT_TAKEN() do { if (lane == 0) V[ZB_V_NOT_TAKEN] = 1; } while (0)
+    if (DUNI(ZB_LOAD_AGENT(&C->mode)) != 1) {
+        if (b != 0 || wv != 0) return;
+        if (origLen != 0) { ZV_NOT_TAKEN(); return; }
+        const uint32_t srcSize = d.src_len >= 28 ? d.src_len - 28 : 0;
+        const DecFrame fh = dec_frame_header(src, srcSize);
+        if (fh.status != TSX_OK) { ZV_NOT_TAKEN(); return; }
+        if (fh.contentSize != 0) { ZV_FAIL(); return; }
+        uint32_t p = fh.p;
+        for (uint32_t k = 0; k < ZB_MAX_BLOCKS; k++) {
+            const DecBlockHdr bh = dec_block_header(src, srcSize, p);
+            if (!bh.ok || bh.btype == 2) break;                         // (a compressed block of nothing: not ours to judge)
+            if (bh.bsize != 0) { ZV_FAIL(); return; }
+            p = bh.next;
+            if (!bh.last) continue;
+            if (!dec_frame_end(p, srcSize, fh.hasChecksum)) break;
+            if (fh.hasChecksum && !dec_checksum_ok(orig, 0, dec_checksum_at(src, p), lane)) { ZV_FAIL(); return; }
+            if (lane == 0) V[ZB_V_SEEN] = 1;
+            return;
+        }
+        ZV_NOT_TAKEN();
+        return;
+    }
+    const uint32_t nb = DUNI(C->nblocks);
+    if (b >= nb) return;
+    const uint8_t* const litArena = arenas + (size_t)chunk * astride;
+    const uint32_t* const seqArena = (const uint32_t*)(litArena + lit_cap);
+    for (uint32_t i = tid; i < nb; i += ZB_SC_WAVES * LANES) {
+        const ZbBlock* const S = &C->blk[i];
+        sRegen[i] = S->regen;
+        sHist[0][i] = S->endHist[0]; sHist[1][i] = S->endHist[1]; sHist[2][i] = S->endHist[2];
+        sFlag[i] = (uint8_t)((S->btype == 2 ? 1 : 0) | (S->ok ? 2 : 0) | (S->nbSeq ? 4 : 0));
+    }
+    __threadfence_block();
+    __syncthreads();
+    uint32_t h0 = 1, h1 = 4, h2 = 8, myStart = 0, regen = 0;
+    {
+        uint32_t pos = 0; bool okAll = true;
+        for (uint32_t i = 0; i < nb; i++) {                             // wave-uniform; O(1) per block; every wave for itself
+            const uint32_t rg = DUNI(sRegen[i]), fl = DUNI(sFlag[i]);
+            if (i == b) { myStart = pos; regen = rg; }
+            if (fl & 1) {
+                if (!(fl & 2)) okAll = false;
+                if (i < b && (fl & 4)) {
+                    const uint32_t e0 = DUNI(sHist[0][i]), e1 = DUNI(sHist[1][i]), e2 = DUNI(sHist[2][i]);
+                    const uint32_t n0 = zb_subst(e0, h0, h1, h2), n1 = zb_subst(e1, h0, h1, h2), n2 = zb_subst(e2, h0, h1, h2);
+                    h0 = n0; h1 = n1; h2 = n2;
+                }
+            }
+            pos += rg;
+            if (pos > ZB_MAX_CHUNK) { okAll = false; break; }
+        }
+        // every workgroup of the chunk sees the same sums.  A block the decode kernel did not finish, or blocks that do not add up to the
+        // frame's own content size: a frame this form does not read - not taken.  A content size that is not the chunk's length: a mismatch
+        if (!okAll || pos != DUNI(C->contentSize)) { if (b == 0 && wv == 0) ZV_NOT_TAKEN(); return; }
+        if (pos != origLen) { if (b == 0 && wv == 0) ZV_FAIL(); return; }
+    }
+    if (b == 0 && tid == 0) V[ZB_V_SEEN] = 1;
+    // every position below is < origLen: the block's bytes are [myStart, myStart + regen) of a sum that equals it
+    const ZbBlock* const B = &C->blk[b];
+    const uint32_t btype = DUNI(B->btype), boff = DUNI(B->off);
+    bool diff = false;
+    if (btype == 0) { for (uint32_t i = tid; i < regen; i += ZB_SC_WAVES * LANES) diff |= orig[myStart + i] != src[boff + i]; }
+    else if (btype == 1) { const uint8_t v = src[boff]; for (uint32_t i = tid; i < regen; i += ZB_SC_WAVES * LANES) diff |= orig[myStart + i] != v; }
+    else {
+        const uint32_t litSize = DUNI(B->litSize), nbSeq = DUNI(B->nbSeq);
+        const uint8_t* litPtr = litArena + DUNI(B->litAt);
+        if (DUNI(B->ltype) == 0) { const DecLit h = dec_lit_header(src + boff, DUNI(B->bsize)); litPtr = src + boff + h.hl; }
+        const uint32_t* const sLL = seqArena + DUNI(B->seqAt); const uint32_t* const sML = sLL + seq_cap; const uint32_t* const sOF = sML + seq_cap;
+        const uint32_t ngroups = (nbSeq + LANES - 1) / LANES;
+        if (ngroups > ZB_SC_GROUPS) { if (wv == 0) ZV_NOT_TAKEN(); return; }         // (the decode kernel bounds the match lengths' sum: cannot happen)
+        // sweep 1: the groups' byte counts
+        for (uint32_t gi = wv; gi < ngroups; gi += ZB_SC_WAVES) {
+            const uint32_t q = gi * LANES + lane;
+            uint32_t a = q < nbSeq ? sLL[q] : 0, t = q < nbSeq ? a + sML[q] : 0;
+            for (int o = 32; o; o >>= 1) { a += __shfl_xor(a, o); t += __shfl_xor(t, o); }
+            if (lane == 0) { sLit[gi] = a; sTot[gi] = t; }
+        }
+        __threadfence_block();
+        __syncthreads();
+        if (wv == 0) {                                                   // exclusive prefixes, 64 groups per step
+            uint32_t cl = 0, ct = 0;
+            for (uint32_t g0 = 0; g0 <= ngroups; g0 += LANES) {
+                const uint32_t gi = g0 + lane;
+                const uint32_t a = gi < ngroups ? sLit[gi] : 0, t = gi < ngroups ? sTot[gi] : 0;
+                uint32_t ia = a, it = t;
+                for (int o = 1; o < LANES; o <<= 1) {
+                    const uint32_t x = __shfl_up(ia, o), y = __shfl_up(it, o);
+                    if (lane >= (uint32_t)o) { ia += x; it += y; }
+                }
+                if (gi <= ngroups) { sLit[gi] = cl + ia - a; sTot[gi] = ct + it - t; }
+                cl += (uint32_t)__builtin_amdgcn_readlane(ia, LANES - 1); ct += (uint32_t)__builtin_amdgcn_readlane(it, LANES - 1);
+            }
+        }
+        __threadfence_block();
+        __syncthreads();
+        const uint32_t allLit = DUNI(sLit[ngroups]), allTot = DUNI(sTot[ngroups]);
+        if (allLit > litSize || allTot + (litSize - allLit) != regen) { if (wv == 0) ZV_NOT_TAKEN(); return; }    // (sums the decode kernel has checked)
+        // sweep 2: every group on its own
+        for (uint32_t gi = wv; gi < ngroups; gi += ZB_SC_WAVES) {
+            const uint32_t g = gi * LANES;
+            const uint32_t cnt = nbSeq - g < LANES ? nbSeq - g : LANES;
+            const uint32_t lp = DUNI(sLit[gi]), opos = myStart + DUNI(sTot[gi]), groupTot = DUNI(sTot[gi + 1]) - DUNI(sTot[gi]);
+            const bool valid = lane < cnt;
+            const uint32_t ll = valid ? sLL[g + lane] : 0, ml = valid ? sML[g + lane] : 0;
+            uint32_t off = valid ? sOF[g + lane] : 0;
+            if (off & ZB_SYM) off = zb_subst(off, h0, h1, h2);
+            uint32_t litIncl = ll, totIncl = ll + ml;
+            for (int o = 1; o < LANES; o <<= 1) {
+                const uint32_t a = __shfl_up(litIncl, o), t = __shfl_up(totIncl, o);
+                if (lane >= (uint32_t)o) { litIncl += a; totIncl += t; }
+            }
+            const uint32_t myLit = lp + litIncl - ll, myOut = opos + totIncl - (ll + ml), mOut = myOut + ll;
+            if (__any(valid && ml && (off == 0 || off > mOut))) { diff = true; break; }       // a match that starts before the chunk does: restores nothing
+            WAVE_SYNC();
+            gStart[wv][lane] = valid ? myOut : opos + groupTot; gLL[wv][lane] = ll; gLit[wv][lane] = myLit; gSrc[wv][lane] = mOut - off;
+            if (lane == 0) gStart[wv][LANES] = opos + groupTot;
+            __threadfence_block();
+            WAVE_SYNC();
+            for (uint32_t p = opos + lane; p < opos + groupTot; p += LANES) {
+                uint32_t i = 0;
+                for (uint32_t s_ = 32; s_; s_ >>= 1) if (gStart[wv][i + s_] <= p) i += s_;     // the last sequence that starts at or before p
+                const uint32_t rel = p - gStart[wv][i], l_ = gLL[wv][i];
+                const uint8_t want = rel < l_ ? litPtr[gLit[wv][i] + rel] : orig[gSrc[wv][i] + (rel - l_)];    // (the source of a match byte is < p)
+                diff |= orig[p] != want;
+            }
+        }
+        // the literals behind the last sequence
+        for (uint32_t k = tid; k < litSize - allLit; k += ZB_SC_WAVES * LANES) diff |= orig[myStart + allTot + k] != litPtr[allLit + k];
+    }
+    if (__any(diff)) ZV_FAIL();
+    // Four wrong checksum bytes make a chunk unreadable to every reader: the last wave of the frame's last block (the short one) hashes the
+    // SOURCE chunk when it is done comparing
+    if (b + 1 == nb && wv == ZB_SC_WAVES - 1 && DUNI(C->hasCksum) && !dec_checksum_ok(orig, origLen, DUNI(C->cksum), lane)) ZV_FAIL();
+#undef ZV_FAIL
+#undef ZV_NOT_TAKEN
+}
+
 // one jump pass: every unresolved word takes its source's word, twice (four words per thread).  Chain depths are small in practice
 // (log-like content: every word resolved after 7 jumps = 4 passes, its matches reach ~100 KB back, not to the previous record) while the
 // launcher must queue the passes the WORST case needs (a 4 MiB chain at offset 1 or 2: three guaranteed hops per pass, 15 passes queued): a pass notes whether it left
@@ -600,4 +777,31 @@ uint32_t tsx_launch_zstd_decompress_blocks(hipStream_t st, const uint8_t* frames
 #endif
     hipLaunchKernelGGL(zb_emit_kernel, dim3((max_out + 4095) / 4096, n), dim3(256), 0, st, (const tsx_chunk_desc*)d_descs, dst, hdrs, arenas, (uint64_t)astride, lit_cap, seq_cap);
     return 4 + rounds;
+}
+
+// ---- verify on upload --------------------------------------------------------------------------------
+// index, decode, verify: three launches.  The workspace is the decoder's without its largest part, the word per output byte:
+// [n chunk headers][n arenas: literals | literal lengths | match lengths | offsets].  max_len: the longest source chunk of the launch
+// (chunks above ZB_MAX_CHUNK are not taken; the arenas are sized for the others).
+static inline uint32_t zb_verify_max(uint32_t max_len) { return max_len < ZB_MAX_CHUNK ? max_len : ZB_MAX_CHUNK; }
+static inline size_t zb_verify_stride(uint32_t max_len) {
+    return ((size_t)zb_lit_cap(zb_verify_max(max_len)) + 12u * (size_t)zb_seq_cap(zb_verify_max(max_len)) + 255u) & ~(size_t)255u;
+}
+size_t tsx_zstd_verify_bytes(uint32_t n, uint32_t max_len) { return (size_t)n * (ZB_CHUNK_HDR_BYTES + zb_verify_stride(max_len)); }
+uint32_t tsx_launch_zstd_verify_blocks(hipStream_t st, const uint8_t* frames, uint64_t mid_stride, const tsx_chunk_desc* d_descs, const int32_t* d_status,
+                                       uint32_t n, uint32_t max_len, const uint8_t* src_base, void* work, uint32_t* verdicts) {
+    if (!n) return 0;
+    uint8_t* const hdrs = (uint8_t*)work;
+    uint8_t* const arenas = hdrs + (size_t)n * ZB_CHUNK_HDR_BYTES;
+    const size_t astride = zb_verify_stride(max_len);
+    const uint32_t lit_cap = zb_lit_cap(zb_verify_max(max_len)), seq_cap = zb_seq_cap(zb_verify_max(max_len));
+    hipLaunchKernelGGL(zb_index_kernel, dim3(n), dim3(LANES), 0, st, frames, 1, mid_stride, d_descs, d_status, hdrs, lit_cap, seq_cap);
+    hipLaunchKernelGGL(zb_decode_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(2 * LANES), 0, st, frames, 1, mid_stride, d_descs, hdrs, arenas, (uint64_t)astride, lit_cap, seq_cap
+#ifdef TSX_PROF2
+                       , (unsigned long long*)nullptr
+#endif
+                       );
+    hipLaunchKernelGGL(zb_verify_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(ZB_SC_WAVES * LANES), 0, st, frames, mid_stride, d_descs, d_status, src_base, hdrs, arenas,
+                       (uint64_t)astride, lit_cap, seq_cap, verdicts);
+    return 3;
 }

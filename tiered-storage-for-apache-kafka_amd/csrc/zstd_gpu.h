@@ -30,3 +30,10 @@ bool tsx_zstd_blockmode_takes(uint32_t max_out);
 const uint32_t* tsx_zstd_blockmode_skip(const void* bwork, uint32_t* stride_words);
 uint32_t tsx_launch_zstd_decompress_blocks(hipStream_t st, const uint8_t* frames, int from_mid, uint64_t mid_stride, tsx_chunk_desc* d_descs, uint32_t n,
                                            uint32_t max_out, uint8_t* dst, int32_t* d_status, void* bwork);
+// Verify on upload (zstd_dec_blocks.hip, zb_verify_kernel): frame i at frames + i * mid_stride, d_descs[i].src_len - 28 bytes, against
+// the chunk it was written from, src_base + d_descs[i].dst_off, d_descs[i].dst_cap bytes; d_status[i] != 0: chunk i is left alone.
+// The parsing kernels of the block-parallel decoder, then a comparison in place of its execution stages: three launches, returned.
+// verdicts: ZB_VERDICT_WORDS (zstd_dec_blocks.h) words per chunk, zero on entry, in memory the host reads.  work: tsx_zstd_verify_bytes(n, max_len).
+size_t tsx_zstd_verify_bytes(uint32_t n, uint32_t max_len);
+uint32_t tsx_launch_zstd_verify_blocks(hipStream_t st, const uint8_t* frames, uint64_t mid_stride, const tsx_chunk_desc* d_descs, const int32_t* d_status,
+                                       uint32_t n, uint32_t max_len, const uint8_t* src_base, void* work, uint32_t* verdicts);

@@ -247,7 +247,7 @@ public:
     GpuTransformChunkEnumeration(std::shared_ptr<Backend> backend, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                  std::optional<DataKeyAndAAD> encryption, IvSupplier ivSupplier = secureRandomIvSupplier(),
                                  int batchChunks = 64, bool withCrc = false, uint32_t zstdProfile = TSX_ZSTD_PROFILE_1_5_7, bool readAhead = true,
-                                 int zstdLevel = 0, bool zstdChecksum = false);
+                                 int zstdLevel = 0, bool zstdChecksum = false, bool zstdVerify = false);
     ~GpuTransformChunkEnumeration() override;
     // Zstandard level of the frames (compression.zstd.level): 0 = the library default (3, what the reference uses), 1, 2 or 3;
     // anything else is refused here, not at the first batch
@@ -255,6 +255,10 @@ public:
     // content checksum in every frame (compression.zstd.checksum, TSX_ZSTD_CHECKSUM): off = the reference's bytes; refused here when
     // the chain does not compress.  (Every fetch verifies a checksum that is there - the fetch side has no option.)
     bool zstdChecksum() const { return checksum_; }
+    // verify on upload (compression.zstd.verify, TSX_VERIFY): every frame is read back on the device and compared with its chunk before
+    // the chunk is handed on; a chunk whose frame does not restore it (TSX_E_VERIFY) raises what any failed chunk raises.  Covers the
+    // frame, not the encryption behind it.  Refused here when the chain does not compress.
+    bool zstdVerify() const { return verify_; }
     int originalChunkSize() const override { return inner_->originalChunkSize(); }
     std::optional<int> transformedChunkSize() const override { return transformedChunkSize_; }
     bool hasMoreElements() override;
@@ -285,6 +289,7 @@ private:
     bool readAhead_;
     int level_;
     bool checksum_;
+    bool verify_;
     std::optional<int> transformedChunkSize_;
     std::vector<Bytes> ready_;
     size_t next_ = 0;
@@ -334,6 +339,7 @@ public:
     const std::vector<uint32_t>& crc32cOfOriginalChunks() const { return crcs_; }
     int zstdLevel() const { return inner_->zstdLevel(); }   // the enumeration's (the finisher transforms through it)
     bool zstdChecksum() const { return inner_->zstdChecksum(); }
+    bool zstdVerify() const { return inner_->zstdVerify(); }
 
 private:
     bool nextBatch();

@@ -6,7 +6,9 @@ transformed / original, and the compressor service's kernel time; a sample of ev
 (+ the oracle's GCM).  One JSON line per run, then a summary line.
 --checksum: every level runs twice per round, with and without a content checksum in its frames (TSX_ZSTD_CHECKSUM), alternating the same
 way; the frames with one are checked against libzstd's own ZSTD_c_checksumFlag frames.
-  python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8] [--levels 3] [--checksum]"""
+--verify: the same for verify on upload (TSX_VERIFY): every level without and with it, alternating (off on, on off, ... in one process); the
+rows of the verifying runs carry the verifier's own time of the last batch (tsx_timing.unzstd_ms, unzstd_launches).
+  python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8] [--levels 3] [--checksum] [--verify]"""
 import argparse
 import ctypes
 import json
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--check", type=int, default=16, help="timed chunks per run checked against libzstd")
     ap.add_argument("--levels", default="1,2,3")
     ap.add_argument("--checksum", action="store_true", help="each level with and without TSX_ZSTD_CHECKSUM, alternating")
+    ap.add_argument("--verify", action="store_true", help="each level without and with TSX_VERIFY, alternating")
     args = ap.parse_args()
 
     import torch  # before libtsxform: one shared HIP runtime
@@ -52,7 +55,8 @@ def main():
     n = args.segments * cps
     T = args.callers
     flags = nat.COMPRESS | nat.ENCRYPT | nat.CRC
-    levels = [(int(x), ck) for x in args.levels.split(",") for ck in ((False, True) if args.checksum else (False,))]
+    levels = [(int(x), ck, vf) for x in args.levels.split(",") for ck in ((False, True) if args.checksum else (False,))
+              for vf in ((False, True) if args.verify else (False,))]
 
     def libzstd_frame(raw, level, checksum):
         """libzstd's frame as oracle/zstd_ref.c makes it, with ZSTD_c_checksumFlag on request."""
@@ -110,8 +114,8 @@ def main():
         order = []
         for r in range(args.rounds):
             order += levels if r % 2 == 0 else levels[::-1]
-        for level, ck in order:
-            p = nat.Native.make_params(flags | (nat.ZSTD_CHECKSUM if ck else 0), synth.KEY, synth.AAD, zstd_level=level)
+        for level, ck, vf in order:
+            p = nat.Native.make_params(flags | (nat.ZSTD_CHECKSUM if ck else 0) | (nat.VERIFY if vf else 0), synth.KEY, synth.AAD, zstd_level=level)
             ds = [d.copy() for _ in range(T)]
 
             def step(t):
@@ -143,7 +147,8 @@ def main():
                 raw = np.ascontiguousarray(host_chunk(i)).tobytes()
                 exp = o.gcm_encrypt_chunk(synth.KEY, ds[0]["iv"][i].tobytes(), synth.AAD, libzstd_frame(raw, level, ck))
                 ok = ok and got == exp
-            row = {"content": content, "level": level, "checksum": ck, "gibs": round(args.steps * n * CH / GiB / el, 3), "elapsed_s": round(el, 3),
+            tm = N.ctx_timing(ctxs[0])
+            row = {"content": content, "level": level, "checksum": ck, "verify": vf, "unzstd_ms": round(tm.unzstd_ms, 2), "unzstd_launches": tm.unzstd_launches, "gibs": round(args.steps * n * CH / GiB / el, 3), "elapsed_s": round(el, 3),
                    "ratio": round(float(ds[0]["dst_len"].astype(np.int64).sum() - 28 * n) / (n * CH), 4),
                    "kernel_ms": round(s1["kernel_ms"] - s0["kernel_ms"], 1), "launches": s1["launches"] - s0["launches"],
                    "chunks": n, "distinct_chunks": distinct, "steps": args.steps, "callers": T,
@@ -152,10 +157,10 @@ def main():
             print(json.dumps(row), flush=True)
     summary = {}
     for r in rows:
-        k = "%s_L%d%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else "")
+        k = "%s_L%d%s%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else "", "_verify" if r["verify"] else "")
         summary.setdefault(k, []).append(r["gibs"])
     print(json.dumps({"metric": "GiB/s of original bytes per level (runs in order)", "runs": summary,
-                      "ratio": {"%s_L%d%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else ""): r["ratio"] for r in rows},
+                      "ratio": {"%s_L%d%s%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else "", "_verify" if r["verify"] else ""): r["ratio"] for r in rows},
                       "all_exact": all(r["exact_vs_libzstd"] for r in rows), "libzstd": o.zstd_version(), "tsxform": N.version()}), flush=True)
 
 
