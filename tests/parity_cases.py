@@ -28,9 +28,9 @@ def make_descs(sizes, soff, doff, caps, segment=0):
     return d
 
 
-def run_transform(N, flags, chunks, key=synth.KEY, aad=synth.AAD, mem=None, profile=nat.ZSTD_PROFILE_1_5_7, dst_caps=None, ctx=None):
+def run_transform(N, flags, chunks, key=synth.KEY, aad=synth.AAD, mem=None, profile=nat.ZSTD_PROFILE_1_5_7, dst_caps=None, ctx=None, segment=0):
     """chunks: list of numpy uint8 arrays.  Returns (list of transformed bytes, descs).  dst_caps: per-chunk override of the
-    slot capacity handed to the library (None = the library's own bound)."""
+    slot capacity handed to the library (None = the library's own bound).  segment: the segment number in the chunks' IVs."""
     sizes = [int(c.size) for c in chunks]
     soff, doff, caps, st, dt = layout(sizes, flags, N)
     if dst_caps:
@@ -39,7 +39,7 @@ def run_transform(N, flags, chunks, key=synth.KEY, aad=synth.AAD, mem=None, prof
     for c, o_ in zip(chunks, soff):
         src[o_:o_ + c.size] = c
     dst = np.zeros(max(dt, 16), np.uint8)
-    d = make_descs(sizes, soff, doff, caps)
+    d = make_descs(sizes, soff, doff, caps, segment=segment)
     p = nat.Native.make_params(flags, key, aad, zstd_profile=profile)
     if mem == "device":
         ds, dd = N.device_malloc(src.size), N.device_malloc(dst.size)
@@ -56,7 +56,7 @@ def run_transform(N, flags, chunks, key=synth.KEY, aad=synth.AAD, mem=None, prof
     return outs, d
 
 
-def run_detransform(N, flags, blobs, out_sizes, key=synth.KEY, aad=synth.AAD, ctx=None):
+def run_detransform(N, flags, blobs, out_sizes, key=synth.KEY, aad=synth.AAD, ctx=None, segment=0):
     sizes = [len(b) for b in blobs]
     soff, st = [], 0
     for s in sizes:
@@ -68,7 +68,7 @@ def run_detransform(N, flags, blobs, out_sizes, key=synth.KEY, aad=synth.AAD, ct
     for b, o_ in zip(blobs, soff):
         src[o_:o_ + len(b)] = np.frombuffer(b, np.uint8)
     dst = np.zeros(max(dt, 16), np.uint8)
-    d = make_descs(sizes, soff, doff, out_sizes)
+    d = make_descs(sizes, soff, doff, out_sizes, segment=segment)
     p = nat.Native.make_params(flags, key, aad)
     N.detransform_batch(p, d, src, dst, dst.size, ctx=ctx)
     outs = [dst[doff[i]:doff[i] + d["dst_len"][i]].tobytes() for i in range(len(sizes))]

@@ -19,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tsxform  # noqa: E402
 from tests import parity_cases as pc  # noqa: E402
+from tests import keying_cases as kc  # noqa: E402
 from tests import level_cases as lc  # noqa: E402
 from tests.fuzz_cases import gen_case, level_case  # noqa: E402
 
@@ -62,11 +63,12 @@ def main():
             if d2["status"][i] != 0 or back[i] != c.tobytes():
                 bad += 1
                 print("DECODE MISMATCH seed %d case %d size %d status %d" % (args.seed, n_cases + i, c.size, d2["status"][i]), file=log, flush=True)
-        if (n_cases // args.batch) % 4 == 0:                       # the chain, fused and with one launch per stage
+        if (n_cases // args.batch) % 4 == 0:                       # the chain, fused and with one launch per stage, under a key, AAD and segment of this round
+            key, aad, seg = kc.draw(rng, int(rng.integers(0, 65)))
             for sep in (0, 1):
                 try:
                     with emu.configured(stages_separate=sep):
-                        pc.check_transform_vs_oracle(emu, o, nat.COMPRESS | nat.ENCRYPT | nat.CRC, cases[:3])
+                        kc.check_keyed(emu, o, nat.COMPRESS | nat.ENCRYPT | nat.CRC, cases[:3], key, aad, seg, "chain")
                 except AssertionError as e:
                     bad += 1
                     print("CHAIN MISMATCH seed %d case %d sep=%r: %s" % (args.seed, n_cases, sep, e), file=log, flush=True)
@@ -122,12 +124,13 @@ def fuzz_guests(args, emu, o, rng, log):
     try:
         while time.time() - t0 < args.seconds:
             cases = [gen_case(rng, total=int(rng.integers(1, 700000))) for _ in range(int(rng.integers(1, args.batch + 1)))]
-            exp = [pc.oracle_transform(o, flags, c, i) for i, c in enumerate(cases)]
+            key, aad, seg = kc.draw(rng, int(rng.integers(0, 65)))
+            exp = kc.expected_blobs(o, flags, key, aad, seg, cases)
             time.sleep(0.003)                                           # quiet again: the next launch has guests
             s0 = emu.service_stats(0)
             after = int(rng.integers(1, 16))
             emu.lib.hipemu_force_yield_after(after)
-            got, d = pc.run_transform(emu, flags, cases, mem="packed" if rng.integers(0, 2) else None, profile=nat.ZSTD_PROFILE_1_5_7)
+            got, d = pc.run_transform(emu, flags, cases, mem="packed" if rng.integers(0, 2) else None, profile=nat.ZSTD_PROFILE_1_5_7, key=key, aad=aad, segment=seg)
             emu.lib.hipemu_force_yield_after(0)
             emu.service_quiesce(0)
             s1 = emu.service_stats(0)
@@ -138,7 +141,7 @@ def fuzz_guests(args, emu, o, rng, log):
                 print("GUEST MISMATCH seed %d case %d after=%d sizes %s statuses %s chunks counted %d" % (args.seed, n_cases, after, [int(c.size) for c in cases], list(d["status"]), s1["device_chunks"] - s0["device_chunks"]), file=log, flush=True)
                 for i, c in enumerate(cases):
                     c.tofile("/tmp/fuzz_guest_bad_%d_%d_%d.bin" % (args.seed, n_cases, i))
-            back, d2 = pc.run_detransform(emu, flags, got, [int(c.size) for c in cases])     # (a fetch: the next launch's guests find the word raised until it is quiet again)
+            back, d2 = pc.run_detransform(emu, flags, got, [int(c.size) for c in cases], key=key, aad=aad)     # (a fetch: the next launch's guests find the word raised until it is quiet again)
             if (d2["status"] != 0).any() or back != [c.tobytes() for c in cases]:
                 bad += 1
                 print("GUEST ROUND TRIP MISMATCH seed %d case %d" % (args.seed, n_cases), file=log, flush=True)

@@ -14,6 +14,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: F401,E402  (one HIP runtime)
 import tsxform  # noqa: E402
 from tests import parity_cases as pc  # noqa: E402
+from tests import keying_cases as kc  # noqa: E402
 from tests import level_cases as lc  # noqa: E402
 from tests.fuzz_cases import LEVEL_WINDOW, gen_case, level_case  # noqa: E402
 
@@ -56,11 +57,11 @@ def main():
     print("[%5.0fs] %d cases, %.1f MB, %d bad" % (time.time() - t0, done, nbytes / 1e6, bad), flush=True)
     for lo in range(0, args.big, 32):
         run([gen_case(rng, 4194304 - int(rng.integers(0, 3)) * int(rng.integers(0, 70000))) for _ in range(min(32, args.big - lo))], "big")
-    # the chain on a sample (CRC head + GCM tail in the compressor wave)
+    # the chain on a sample (CRC head + GCM tail in the compressor wave), under a key, AAD and segment drawn from the seed, and back
     sample = [gen_case(rng) for _ in range(96)] + [gen_case(rng, 4194304) for _ in range(4)]
+    key, aad, seg = kc.draw(rng, int(rng.integers(0, 65)))
     try:
-        pc.check_transform_vs_oracle(N, o, nat.COMPRESS | nat.ENCRYPT | nat.CRC, sample)
-        pc.check_roundtrip(N, nat.COMPRESS | nat.ENCRYPT | nat.CRC, sample)
+        kc.check_keyed(N, o, nat.COMPRESS | nat.ENCRYPT | nat.CRC, sample, key, aad, seg, "chain")
     except AssertionError as e:
         bad += 1; print("CHAIN MISMATCH:", e, flush=True)
     print("DONE seed %d: %d cases (%d of 4 MiB), %.1f MB, %d bad, %.0f s; libzstd %s" % (args.seed, done, args.big, nbytes / 1e6, bad, time.time() - t0, o.zstd_version()), flush=True)
