@@ -1,4 +1,4 @@
-// TEST HARNESS ONLY: the front end of libtsxform (csrc/tsx_api.hip: compressor service, context pools, device hints, copy pipeline) under
+// TEST HARNESS ONLY: the front end of libtsxform (csrc/tsx_api.hip, csrc/tsx_batch.hip: compressor service, context pools, device hints, copy pipeline) under
 // ThreadSanitizer.  The kernel sources are compiled for the CPU emulator (tests/emu) with -fsanitize=thread and linked with this driver
 // (`make -C csrc emu-tsan`): T threads issue context-less compressing batches (the broker's shape: members of the device's service queue), inverse
 // batches, CRC-only batches and batches on explicit contexts at the same time; every result must equal the single-threaded one, and the
@@ -54,7 +54,7 @@ int main(int argc, char** argv) {
             d.src_off = off; d.src_len = sizes[i]; d.dst_off = (uint64_t)i * j.slot; d.dst_cap = (uint32_t)j.slot;
             for (int k = 0; k < 12; k++) d.iv[k] = (uint8_t)(k + i + 16 * t);
             j.src.insert(j.src.end(), c.begin(), c.end()); off += sizes[i];
-            while (off & 15) { j.src.push_back(0); off++; }              // slots are 16-byte aligned (tsx_api.hip validate)
+            while (off & 15) { j.src.push_back(0); off++; }              // slots are 16-byte aligned (tsx_batch.hip validate)
             j.d.push_back(d);
         }
         if (j.src.empty()) j.src.push_back(0);

@@ -107,7 +107,7 @@ def test_no_kernel_on_the_fetch_path_uses_scratch(product_lib):
     """A queue's first dispatch that needs scratch makes the runtime (re)size that queue's scratch, and while the compressor service's
     long-lived kernel holds its own the request waits for that kernel to END: the first fetch after uploads began took 18.6 s on the device
     (every later one 4 ms).  So only two kernels of the library may have a private segment at all - the compressor itself and the batch
-    build of the chunk-serial decoder, which is never launched while the service is alive (tsx_api.hip launch_stages).  Read from the
+    build of the chunk-serial decoder, which is never launched while the service is alive (tsx_batch.hip launch_stages).  Read from the
     compiler's resource report of the build that produced libtsxform.so (csrc/Makefile)."""
     obj = os.path.join(PKG, "csrc", "_obj")
     reports = [f for f in os.listdir(obj) if f.endswith(".usage.txt")] if os.path.isdir(obj) else []

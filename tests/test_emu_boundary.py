@@ -1,4 +1,4 @@
-"""The C-ABI front end (csrc/tsx_api.hip) under the CPU emulator: device selection of the ctx-less calls, pooled contexts,
+"""The C-ABI front end (csrc/tsx_api.hip, csrc/tsx_batch.hip) under the CPU emulator: device selection of the ctx-less calls, pooled contexts,
 the staged host-memory pipeline, key hygiene, failed-chunk scrubbing and argument validation.  Same source as the product
 library; the GPU twins of the data-path cases are in tests/test_gpu_parity.py."""
 import os

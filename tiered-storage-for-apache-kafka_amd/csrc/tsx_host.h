@@ -1,5 +1,5 @@
-// What the host-side translation units share (tsx_api.hip: devices, contexts, batch pipelines; tsx_service.hip: the compressor service):
-// the configuration, error reporting, the device record.
+// What the host-side translation units share (tsx_api.hip: devices, contexts, entry points; tsx_batch.hip: the batch pipelines;
+// tsx_service.hip: the compressor service): the configuration, error reporting, the device record.  (Contexts and batches: tsx_ctx.h.)
 #pragma once
 #include <memory>
 #include <utility>
@@ -57,7 +57,7 @@ struct tsx_device_scope {
 };
 
 struct tsx_ctx;
-struct tsx_verifier;                                         // tsx_api.hip: the device's verify-on-upload workspace
+struct tsx_verifier;                                         // tsx_batch.hip: the device's verify-on-upload workspace
 struct tsx_service;                                          // tsx_service.hip: nobody else looks inside
 struct tsx_service_delete { void operator()(tsx_service* s) const; };
 
@@ -77,7 +77,7 @@ struct tsx_device {
     size_t idle_cap = 0;                                     // most idle workspace kept (init_devices: a fraction of THIS device's memory)
     std::vector<std::pair<void*, size_t>> spare_bwork;       // block-form decoder workspaces that left their context (pool_release), for the next one
     std::unique_ptr<tsx_service, tsx_service_delete> svc;
-    tsx_verifier* verifier = nullptr;                        // created by the first verifying batch (under g_mu), freed with the device
+    tsx_verifier* verifier = nullptr;                        // created by the first verifying batch (verifier_of), freed with the device
     // copy streams of the context-less compressing calls, shared by the callers: ONE of each.  With a stream per caller a segment's copies
     // stood behind other callers' in the engines' queues anyway, and more streams measured worse (profiles/r04_broker_shape_experiments.txt).
     hipStream_t copy_in = nullptr, copy_out = nullptr;

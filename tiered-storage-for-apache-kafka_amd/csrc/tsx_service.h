@@ -1,4 +1,4 @@
-// The compressor service, host side, as the front end (tsx_api.hip) sees it: a device's service is created with the device, batches that
+// The compressor service, host side, as the front end (tsx_api.hip, tsx_batch.hip) sees it: a device's service is created with the device, batches that
 // compress become its members, everything that frees memory or runs ordinary kernels tells it.  What is inside tsx_service - the queue,
 // the launches, their timing - is tsx_service.hip's alone.  (Also there: tsx_service_quiesce, tsx_service_stats, tsx_debug_service_seed.)
 #pragma once
@@ -18,6 +18,13 @@ svc_geometry svc_geometry_of(const tsx_device& d);
 // as it was before
 void svc_foreground_begin(tsx_device* dev);
 void svc_foreground_end(tsx_device* dev, bool traffic = true);
+struct svc_foreground_scope {                               // begin ... end(dev) around a scope; dev == nullptr: nothing is claimed
+    tsx_device* d;
+    explicit svc_foreground_scope(tsx_device* dev) : d(dev) { if (d) svc_foreground_begin(d); }
+    ~svc_foreground_scope() { if (d) svc_foreground_end(d); }
+    svc_foreground_scope(const svc_foreground_scope&) = delete;
+    svc_foreground_scope& operator=(const svc_foreground_scope&) = delete;
+};
 
 // Is the launch out, or are members waiting for one?  (What launch_stages asks before a decode that would need scratch.)
 bool svc_busy(tsx_device* dev);

@@ -9,5 +9,5 @@ tmp=$(mktemp -d); mkdir -p $tmp/tiered-storage-for-apache-kafka_amd/csrc
 cp $C/*.h $C/zstd_dec.hip $tmp/tiered-storage-for-apache-kafka_amd/csrc/; mkdir -p $tmp/include; cp $ROOT/include/tsxform.h $tmp/include/
 for p in "$@"; do (cd $tmp && patch -s -p1 < $p); done
 (cd $tmp/tiered-storage-for-apache-kafka_amd/csrc && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-value -c zstd_dec.hip -o $C/_obj/dec_$tag.o)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/tiered-storage-for-apache-kafka_amd/libtsxform_dec_$tag.so $C/_obj/tsx_api.o $C/_obj/tsx_service.o $C/_obj/crc32c.o $C/_obj/gcm.o $C/_obj/zstd_enc.o $C/_obj/dec_$tag.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/tiered-storage-for-apache-kafka_amd/libtsxform_dec_$tag.so $C/_obj/tsx_api.o $C/_obj/tsx_batch.o $C/_obj/tsx_service.o $C/_obj/crc32c.o $C/_obj/gcm.o $C/_obj/zstd_enc.o $C/_obj/dec_$tag.o
 rm -rf $tmp; ls -la $ROOT/tiered-storage-for-apache-kafka_amd/libtsxform_dec_$tag.so

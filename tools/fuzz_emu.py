@@ -26,11 +26,16 @@ from tests.fuzz_cases import gen_case, level_case  # noqa: E402
 nat = tsxform._native
 
 
+def more(args, t0, batches):
+    return time.time() - t0 < args.seconds and (not args.batches or batches < args.batches)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=600)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--batch", type=int, default=6)
+    ap.add_argument("--batches", type=int, default=0, help="stop after this many batches (0: when --seconds are over): the same cases on two builds")
     ap.add_argument("--out", default="")
     ap.add_argument("--level", type=int, choices=(1, 2, 3), default=3)
     ap.add_argument("--guests", action="store_true", help="fuzz the guest waves' hand-back instead: every launch's first workgroup sits on the reserved CU and is "
@@ -48,7 +53,7 @@ def main():
         return fuzz_guests(args, emu, o, rng, log)
     if args.level != 3:
         return fuzz_fast(args, emu, o, rng, log)
-    while time.time() - t0 < args.seconds:
+    while more(args, t0, n_cases // args.batch):
         cases = [gen_case(rng) for _ in range(args.batch)]
         outs, d = pc.run_transform(emu, nat.COMPRESS, cases)
         for i, c in enumerate(cases):
@@ -83,7 +88,7 @@ def fuzz_fast(args, emu, o, rng, log):
     and in every other batch a big one (straddling the window's low edge, or structured and W .. W + 300000 bytes long)."""
     level = args.level
     t0 = time.time(); n_cases = 0; n_bytes = 0; bad = 0; batches = 0
-    while time.time() - t0 < args.seconds:
+    while more(args, t0, batches):
         kinds = ["small"] * max(args.batch - 2, 1) + [("collision", "accel")[batches % 2]] + ([("straddle", "big")[(batches // 2) % 2]] if batches % 2 else [])
         cases = [level_case(rng, level, k) for k in kinds]
         outs, d = lc.run_transform(emu, nat.COMPRESS, cases, level)
@@ -118,11 +123,12 @@ def fuzz_guests(args, emu, o, rng, log):
     for f in ("hipemu_cu_key_shift", "hipemu_force_yield_after"):
         getattr(emu.lib, f).argtypes = [ctypes.c_int]; getattr(emu.lib, f).restype = None
     flags = nat.COMPRESS | nat.ENCRYPT | nat.CRC
-    t0 = time.time(); n_cases = 0; n_bytes = 0; bad = 0; handed = 0
+    t0 = time.time(); n_cases = 0; n_bytes = 0; bad = 0; handed = 0; batches = 0
     emu.debug_config("fetch_quiet_ms", 1)
     emu.lib.hipemu_cu_key_shift(3)
     try:
-        while time.time() - t0 < args.seconds:
+        while more(args, t0, batches):
+            batches += 1
             cases = [gen_case(rng, total=int(rng.integers(1, 700000))) for _ in range(int(rng.integers(1, args.batch + 1)))]
             key, aad, seg = kc.draw(rng, int(rng.integers(0, 65)))
             exp = kc.expected_blobs(o, flags, key, aad, seg, cases)
