@@ -55,6 +55,15 @@ __device__ static inline uint32_t zb_subst(uint32_t v, uint32_t h0, uint32_t h1,
     return r - ZB_SYM_DEC(v);                                           // 0 or wrapped when the frame is corrupt: caught where it is used
 }
 
+// A chunk's arena: literals | literal lengths | match lengths | offsets (seq_cap words each) | one word per output byte (the decoder
+// only: zb_arena_stride and zb_verify_stride differ by that array)
+__host__ __device__ static inline size_t zb_arena_words_at(uint32_t lit_cap, uint32_t seq_cap) { return (size_t)lit_cap + 12u * (size_t)seq_cap; }
+struct ZbArena { uint8_t* lit; uint32_t* seq; uint32_t* words; };
+__device__ static inline ZbArena zb_arena(uint8_t* arenas, uint32_t chunk, uint64_t astride, uint32_t lit_cap, uint32_t seq_cap) {
+    uint8_t* const base = arenas + (size_t)chunk * astride;
+    return ZbArena{base, (uint32_t*)(base + lit_cap), (uint32_t*)(base + zb_arena_words_at(lit_cap, seq_cap))};
+}
+
 // ---------------------------------------------------------------------------------------------------
 // index: one wave per chunk
 // ---------------------------------------------------------------------------------------------------
@@ -180,7 +189,9 @@ __global__ __launch_bounds__(LANES) void zb_index_kernel(const uint8_t* __restri
 static unsigned long long* g_zbprof_out = nullptr;                    // 8 u64 per (chunk, block): phase laps of zb_decode_kernel (tools/zb_phase_laps.py)
 extern "C" void tsx_debug_set_zbprof(void* dev_ptr) { g_zbprof_out = (unsigned long long*)dev_ptr; }
 #define ZLT(k) do { const unsigned long long n_ = (unsigned long long)clock64(); zlt_[k] += n_ - zlast_; zlast_ = n_; } while (0)
+#define ZB_PROF_OUT g_zbprof_out
 #else
+#define ZB_PROF_OUT ((unsigned long long*)nullptr)
 #define ZLT(k) do {} while (0)
 #endif
 
@@ -202,15 +213,14 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
     if (DUNI(B->btype) != 2) return;
     const tsx_chunk_desc d = descs[chunk];
     const uint8_t* __restrict__ src = from_mid ? frames + (uint64_t)chunk * mid_stride : frames + d.src_off;
-    uint8_t* const litArena = arenas + (size_t)chunk * astride;
-    uint32_t* const seqArena = (uint32_t*)(litArena + lit_cap);
+    const ZbArena A = zb_arena(arenas, chunk, astride, lit_cap, seq_cap);
     const uint8_t* const blk = src + DUNI(B->off);
     const uint32_t bsize = DUNI(B->bsize);
     if (role == 1) {
         // ---- literals ----
         const DecLit h = dec_lit_header(blk, bsize);                      // (validated by the index kernel)
         if (h.ltype == 0) return;                                       // raw literals are read in place
-        uint8_t* const lit = litArena + DUNI(B->litAt);
+        uint8_t* const lit = A.lit + DUNI(B->litAt);
         if (h.ltype == 1) { const uint8_t v = blk[h.hl]; for (uint32_t i = lane; i < h.litSize; i += LANES) lit[i] = v; return; }
         uint32_t t = h.hl;
         const uint8_t* tree = blk + h.hl; uint32_t treeAvail = h.csize;
@@ -255,7 +265,7 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
         if (dec_seq_table(L, k, mode, src + DUNI(S->off) + to, sb - to, lane) < 0) ZB_FAIL();
     }
     ZLT(0);
-    uint32_t* const sLL = seqArena + DUNI(B->seqAt); uint32_t* const sML = sLL + seq_cap; uint32_t* const sOF = sML + seq_cap;
+    uint32_t* const sLL = A.seq + DUNI(B->seqAt); uint32_t* const sML = sLL + seq_cap; uint32_t* const sOF = sML + seq_cap;
     const uint32_t t = DUNI(B->streamOff);
     DecSeqStream stream = {blk + t, bsize - t, 0, 0, 0};                // n >= 1 (index kernel)
     uint32_t r0 = ZB_SYM, r1 = ZB_SYM | (1u << 28), r2 = ZB_SYM | (2u << 28);      // the history this block starts from, whatever it is
@@ -326,78 +336,77 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
 // ---------------------------------------------------------------------------------------------------
 #define ZB_LIT 0x80000000u                      /* src word: ZB_LIT | byte (resolved), else the chunk position this byte copies from */
 
+__device__ __forceinline__ static void zb_incl_scan2(uint32_t& a, uint32_t& t, uint32_t lane) {      // inclusive scan of two values over the wave
+    for (int o = 1; o < LANES; o <<= 1) { const uint32_t x = __shfl_up(a, o), y = __shfl_up(t, o); if (lane >= (uint32_t)o) { a += x; t += y; } }
+}
+
+// ---- the block walk: what zb_scatter_kernel and zb_verify_kernel share ----
 // One workgroup of ZB_SC_WAVES waves per block.  Every wave walks the block summaries (positions, incoming repeat-offset history:
 // O(1) per block, wave-uniform), the waves share out the block's groups of 64 sequences: a first sweep leaves every group's literal
-// and output byte counts in LDS, their prefix sums place the groups, and then every group is scattered on its own - one word per
-// output byte.  (One wave per block took 0.9 ms of a single chunk's 2.7 ms: ~85 groups one after the other, each behind its own
-// loads - profiles/r03_dec_single_chunk_kernel_stats.txt.)
+// and output byte counts in LDS, their prefix sums place the groups, and then every group is walked on its own - every output byte
+// goes to the kernel's functor once.  (One wave per block took 0.9 ms of a single chunk's 2.7 ms: ~85 groups one after the other, each
+// behind its own loads - profiles/r03_dec_single_chunk_kernel_stats.txt.)  Both helpers are entered and left by whole workgroups.
 #define ZB_SC_WAVES 8u
 #define ZB_SC_GROUPS ((ZS_BLOCK_MAX / 3u + LANES - 1) / LANES + 1)      /* a sequence regenerates >= 3 bytes, a block <= 128 KiB */
-__global__ __launch_bounds__(ZB_SC_WAVES * LANES) void zb_scatter_kernel(const uint8_t* __restrict__ frames, int from_mid, uint64_t mid_stride,
-                                                                         tsx_chunk_desc* __restrict__ descs, uint8_t* __restrict__ hdrs, uint8_t* __restrict__ arenas,
-                                                                         uint64_t astride, uint32_t lit_cap, uint32_t seq_cap) {
-    __shared__ uint32_t sRegen[ZB_MAX_BLOCKS];                          // regenerated size of every block
-    __shared__ uint32_t sHist[3][ZB_MAX_BLOCKS];                        // outgoing history of every block (symbolic in its incoming one)
-    __shared__ uint8_t sFlag[ZB_MAX_BLOCKS];                            // 1 compressed, 2 decoded fine, 4 has sequences
-    __shared__ uint32_t sLit[ZB_SC_GROUPS + 1], sTot[ZB_SC_GROUPS + 1]; // per group of 64 sequences: literal / output bytes, then their exclusive prefixes
-    __shared__ uint32_t gStart[ZB_SC_WAVES][LANES + 1], gLL[ZB_SC_WAVES][LANES], gLit[ZB_SC_WAVES][LANES], gSrc[ZB_SC_WAVES][LANES];   // the group a wave is scattering
-    __shared__ uint32_t sFail;
-    const uint32_t tid = threadIdx.x, lane = tid & (LANES - 1), wv = DUNI(tid >> 6), b = blockIdx.x, chunk = blockIdx.y;
-    ZbChunk* const C = (ZbChunk*)(hdrs + (size_t)chunk * ZB_CHUNK_HDR_BYTES);
-    if (DUNI(ZB_LOAD_AGENT(&C->mode)) != 1) return;
-    const uint32_t nb = DUNI(C->nblocks);
-    if (b >= nb) return;
-    const tsx_chunk_desc d = descs[chunk];
-    const uint8_t* __restrict__ src = from_mid ? frames + (uint64_t)chunk * mid_stride : frames + d.src_off;
-    const uint8_t* const litArena = arenas + (size_t)chunk * astride;
-    const uint32_t* const seqArena = (const uint32_t*)(litArena + lit_cap);
-    uint32_t* const words = (uint32_t*)(litArena + lit_cap + 12u * (size_t)seq_cap);      // one per output byte
+struct ZbWalkLds {
+    uint32_t regen[ZB_MAX_BLOCKS];                                      // regenerated size of every block
+    uint32_t hist[3][ZB_MAX_BLOCKS];                                    // outgoing history of every block (symbolic in its incoming one)
+    uint8_t flag[ZB_MAX_BLOCKS];                                        // 1 compressed, 2 decoded fine, 4 has sequences
+    uint32_t lit[ZB_SC_GROUPS + 1], tot[ZB_SC_GROUPS + 1];              // per group of 64 sequences: literal / output bytes, then their exclusive prefixes
+    uint32_t gStart[ZB_SC_WAVES][LANES + 1], gLL[ZB_SC_WAVES][LANES], gLit[ZB_SC_WAVES][LANES], gSrc[ZB_SC_WAVES][LANES];   // the group a wave is walking
+};
+struct ZbWalk {
+    uint32_t h0, h1, h2, start, regen, total;                           // the history block b starts from, its first output position and size, the sum over all blocks
+    bool ok;                                                            // every compressed block was decoded and the sum stays within ZB_MAX_CHUNK
+};
+// block summaries into LDS, barrier, the walk to block b (wave-uniform; every wave for itself; every workgroup of the chunk sees the same sums)
+__device__ __forceinline__ static ZbWalk zb_walk_to(ZbWalkLds& L, const ZbChunk* C, uint32_t nb, uint32_t b, uint32_t tid) {
     for (uint32_t i = tid; i < nb; i += ZB_SC_WAVES * LANES) {
         const ZbBlock* const S = &C->blk[i];
-        sRegen[i] = S->regen;
-        sHist[0][i] = S->endHist[0]; sHist[1][i] = S->endHist[1]; sHist[2][i] = S->endHist[2];
-        sFlag[i] = (uint8_t)((S->btype == 2 ? 1 : 0) | (S->ok ? 2 : 0) | (S->nbSeq ? 4 : 0));
+        L.regen[i] = S->regen;
+        L.hist[0][i] = S->endHist[0]; L.hist[1][i] = S->endHist[1]; L.hist[2][i] = S->endHist[2];
+        L.flag[i] = (uint8_t)((S->btype == 2 ? 1 : 0) | (S->ok ? 2 : 0) | (S->nbSeq ? 4 : 0));
     }
-    if (tid == 0) sFail = 0;
     __threadfence_block();
     __syncthreads();
-    uint32_t h0 = 1, h1 = 4, h2 = 8, myStart = 0, regen = 0;
-    {
-        uint32_t pos = 0; bool okAll = true;
-        for (uint32_t i = 0; i < nb; i++) {                             // wave-uniform; O(1) per block; every wave for itself
-            const uint32_t rg = DUNI(sRegen[i]), fl = DUNI(sFlag[i]);
-            if (i == b) { myStart = pos; regen = rg; }
-            if (fl & 1) {
-                if (!(fl & 2)) okAll = false;
-                if (i < b && (fl & 4)) {
-                    const uint32_t e0 = DUNI(sHist[0][i]), e1 = DUNI(sHist[1][i]), e2 = DUNI(sHist[2][i]);
-                    const uint32_t n0 = zb_subst(e0, h0, h1, h2), n1 = zb_subst(e1, h0, h1, h2), n2 = zb_subst(e2, h0, h1, h2);
-                    h0 = n0; h1 = n1; h2 = n2;
-                }
+    ZbWalk w = {1, 4, 8, 0, 0, 0, true};
+    for (uint32_t i = 0; i < nb; i++) {                                 // O(1) per block
+        const uint32_t rg = DUNI(L.regen[i]), fl = DUNI(L.flag[i]);
+        if (i == b) { w.start = w.total; w.regen = rg; }
+        if (fl & 1) {
+            if (!(fl & 2)) w.ok = false;
+            if (i < b && (fl & 4)) {
+                const uint32_t e0 = DUNI(L.hist[0][i]), e1 = DUNI(L.hist[1][i]), e2 = DUNI(L.hist[2][i]);
+                const uint32_t n0 = zb_subst(e0, w.h0, w.h1, w.h2), n1 = zb_subst(e1, w.h0, w.h1, w.h2), n2 = zb_subst(e2, w.h0, w.h1, w.h2);
+                w.h0 = n0; w.h1 = n1; w.h2 = n2;
             }
-            pos += rg;
-            if (pos > ZB_MAX_CHUNK) { okAll = false; break; }
         }
-        if (!okAll || pos != DUNI(C->contentSize)) { if (tid == 0) ZB_STORE_AGENT(&C->mode, 0u); return; }       // every wave of the chunk sees the same sums
+        w.total += rg;
+        if (w.total > ZB_MAX_CHUNK) { w.ok = false; break; }
     }
-    const ZbBlock* const B = &C->blk[b];
-    const uint32_t btype = DUNI(B->btype), boff = DUNI(B->off);
-    const uint32_t contentSize = DUNI(C->contentSize);
-    if (b == 0 && tid == 0) descs[chunk].dst_len = contentSize;
-    if (btype == 0) { for (uint32_t i = tid; i < regen; i += ZB_SC_WAVES * LANES) words[myStart + i] = ZB_LIT | src[boff + i]; return; }
-    if (btype == 1) { const uint32_t v = ZB_LIT | src[boff]; for (uint32_t i = tid; i < regen; i += ZB_SC_WAVES * LANES) words[myStart + i] = v; return; }
+    return w;
+}
+// A compressed block: f(p, isLiteral, v) once for every output position p of [w.start, w.start + w.regen) - v is the byte when it is
+// a literal, else the chunk position it copies from (< p).  ZB_WALK_SUMS: the sequences' sums do not fit the block (the decode kernel
+// has checked them: cannot happen) - workgroup-uniform, returned before any byte.  ZB_WALK_REACH: a match of one of this wave's groups
+// starts before the chunk does - wave-uniform; the wave has left its other groups out and done its share of the trailing literals.
+enum : uint32_t { ZB_WALK_OK, ZB_WALK_SUMS, ZB_WALK_REACH };
+template <class F>
+__device__ __forceinline__ static uint32_t zb_walk_block(ZbWalkLds& L, const ZbBlock* B, const uint8_t* __restrict__ src, const ZbArena& A, uint32_t seq_cap,
+                                                         const ZbWalk& w, uint32_t tid, F f) {
+    const uint32_t lane = tid & (LANES - 1), wv = DUNI(tid >> 6), boff = DUNI(B->off);
     const uint32_t litSize = DUNI(B->litSize), nbSeq = DUNI(B->nbSeq);
-    const uint8_t* litPtr = litArena + DUNI(B->litAt);
+    const uint8_t* litPtr = A.lit + DUNI(B->litAt);
     if (DUNI(B->ltype) == 0) { const DecLit h = dec_lit_header(src + boff, DUNI(B->bsize)); litPtr = src + boff + h.hl; }
-    const uint32_t* const sLL = seqArena + DUNI(B->seqAt); const uint32_t* const sML = sLL + seq_cap; const uint32_t* const sOF = sML + seq_cap;
+    const uint32_t* const sLL = A.seq + DUNI(B->seqAt); const uint32_t* const sML = sLL + seq_cap; const uint32_t* const sOF = sML + seq_cap;
     const uint32_t ngroups = (nbSeq + LANES - 1) / LANES;
-    if (ngroups > ZB_SC_GROUPS) { if (tid == 0) ZB_STORE_AGENT(&C->mode, 0u); return; }   // (the decode kernel bounds the match lengths' sum: cannot happen)
+    if (ngroups > ZB_SC_GROUPS) return ZB_WALK_SUMS;                    // (the decode kernel bounds the match lengths' sum)
     // sweep 1: the groups' byte counts
     for (uint32_t gi = wv; gi < ngroups; gi += ZB_SC_WAVES) {
         const uint32_t q = gi * LANES + lane;
         uint32_t a = q < nbSeq ? sLL[q] : 0, t = q < nbSeq ? a + sML[q] : 0;
         for (int o = 32; o; o >>= 1) { a += __shfl_xor(a, o); t += __shfl_xor(t, o); }
-        if (lane == 0) { sLit[gi] = a; sTot[gi] = t; }
+        if (lane == 0) { L.lit[gi] = a; L.tot[gi] = t; }
     }
     __threadfence_block();
     __syncthreads();
@@ -405,54 +414,77 @@ __global__ __launch_bounds__(ZB_SC_WAVES * LANES) void zb_scatter_kernel(const u
         uint32_t cl = 0, ct = 0;
         for (uint32_t g0 = 0; g0 <= ngroups; g0 += LANES) {
             const uint32_t gi = g0 + lane;
-            const uint32_t a = gi < ngroups ? sLit[gi] : 0, t = gi < ngroups ? sTot[gi] : 0;
+            const uint32_t a = gi < ngroups ? L.lit[gi] : 0, t = gi < ngroups ? L.tot[gi] : 0;
             uint32_t ia = a, it = t;
-            for (int o = 1; o < LANES; o <<= 1) {
-                const uint32_t x = __shfl_up(ia, o), y = __shfl_up(it, o);
-                if (lane >= (uint32_t)o) { ia += x; it += y; }
-            }
-            if (gi <= ngroups) { sLit[gi] = cl + ia - a; sTot[gi] = ct + it - t; }
+            zb_incl_scan2(ia, it, lane);
+            if (gi <= ngroups) { L.lit[gi] = cl + ia - a; L.tot[gi] = ct + it - t; }
             cl += (uint32_t)__builtin_amdgcn_readlane(ia, LANES - 1); ct += (uint32_t)__builtin_amdgcn_readlane(it, LANES - 1);
         }
     }
     __threadfence_block();
     __syncthreads();
-    const uint32_t allLit = DUNI(sLit[ngroups]), allTot = DUNI(sTot[ngroups]);
-    if (allLit > litSize || allTot + (litSize - allLit) != regen) { if (tid == 0) ZB_STORE_AGENT(&C->mode, 0u); return; }    // (sums the decode kernel has checked)
+    const uint32_t allLit = DUNI(L.lit[ngroups]), allTot = DUNI(L.tot[ngroups]);
+    if (allLit > litSize || allTot + (litSize - allLit) != w.regen) return ZB_WALK_SUMS;
     // sweep 2: every group on its own
-    bool fail = false;
+    uint32_t res = ZB_WALK_OK;
     for (uint32_t gi = wv; gi < ngroups; gi += ZB_SC_WAVES) {
         const uint32_t g = gi * LANES;
         const uint32_t cnt = nbSeq - g < LANES ? nbSeq - g : LANES;
-        const uint32_t lp = DUNI(sLit[gi]), opos = myStart + DUNI(sTot[gi]), groupTot = DUNI(sTot[gi + 1]) - DUNI(sTot[gi]);
+        const uint32_t lp = DUNI(L.lit[gi]), opos = w.start + DUNI(L.tot[gi]), groupTot = DUNI(L.tot[gi + 1]) - DUNI(L.tot[gi]);
         const bool valid = lane < cnt;
         const uint32_t ll = valid ? sLL[g + lane] : 0, ml = valid ? sML[g + lane] : 0;
         uint32_t off = valid ? sOF[g + lane] : 0;
-        if (off & ZB_SYM) off = zb_subst(off, h0, h1, h2);
+        if (off & ZB_SYM) off = zb_subst(off, w.h0, w.h1, w.h2);
         uint32_t litIncl = ll, totIncl = ll + ml;
-        for (int o = 1; o < LANES; o <<= 1) {
-            const uint32_t a = __shfl_up(litIncl, o), t = __shfl_up(totIncl, o);
-            if (lane >= (uint32_t)o) { litIncl += a; totIncl += t; }
-        }
+        zb_incl_scan2(litIncl, totIncl, lane);
         const uint32_t myLit = lp + litIncl - ll, myOut = opos + totIncl - (ll + ml), mOut = myOut + ll;
-        if (__any(valid && ml && (off == 0 || off > mOut))) { fail = true; break; }
-        // the group's ~1.5 KB of output, one word per byte, written by all lanes side by side: position -> its sequence by a
-        // binary search over the 64 start positions (a lane walking its own run would serialise a 100 KB match on one lane)
+        if (__any(valid && ml && (off == 0 || off > mOut))) { res = ZB_WALK_REACH; break; }
+        // the group's ~1.5 KB of output, all lanes side by side: position -> its sequence by a binary search over the 64 start
+        // positions (a lane walking its own run would serialise a 100 KB match on one lane)
         WAVE_SYNC();
-        gStart[wv][lane] = valid ? myOut : opos + groupTot; gLL[wv][lane] = ll; gLit[wv][lane] = myLit; gSrc[wv][lane] = mOut - off;
-        if (lane == 0) gStart[wv][LANES] = opos + groupTot;
+        L.gStart[wv][lane] = valid ? myOut : opos + groupTot; L.gLL[wv][lane] = ll; L.gLit[wv][lane] = myLit; L.gSrc[wv][lane] = mOut - off;
+        if (lane == 0) L.gStart[wv][LANES] = opos + groupTot;
         __threadfence_block();
         WAVE_SYNC();
         for (uint32_t p = opos + lane; p < opos + groupTot; p += LANES) {
             uint32_t i = 0;
-            for (uint32_t s_ = 32; s_; s_ >>= 1) if (gStart[wv][i + s_] <= p) i += s_;     // the last sequence that starts at or before p
-            const uint32_t rel = p - gStart[wv][i], l_ = gLL[wv][i];
-            words[p] = rel < l_ ? (ZB_LIT | litPtr[gLit[wv][i] + rel]) : gSrc[wv][i] + (rel - l_);
+            for (uint32_t s_ = 32; s_; s_ >>= 1) if (L.gStart[wv][i + s_] <= p) i += s_;     // the last sequence that starts at or before p
+            const uint32_t rel = p - L.gStart[wv][i], l_ = L.gLL[wv][i]; const bool isLit = rel < l_;
+            f(p, isLit, isLit ? (uint32_t)litPtr[L.gLit[wv][i] + rel] : L.gSrc[wv][i] + (rel - l_));
         }
     }
-    if (fail && lane == 0) sFail = 1;
     // the literals behind the last sequence
-    for (uint32_t k = tid; k < litSize - allLit; k += ZB_SC_WAVES * LANES) words[myStart + allTot + k] = ZB_LIT | litPtr[allLit + k];
+    for (uint32_t k = tid; k < litSize - allLit; k += ZB_SC_WAVES * LANES) f(w.start + allTot + k, true, (uint32_t)litPtr[allLit + k]);
+    return res;
+}
+
+// scatter: ONE WORD PER OUTPUT BYTE - the byte itself for a literal, the position it copies from for a match byte
+__global__ __launch_bounds__(ZB_SC_WAVES * LANES) void zb_scatter_kernel(const uint8_t* __restrict__ frames, int from_mid, uint64_t mid_stride,
+                                                                         tsx_chunk_desc* __restrict__ descs, uint8_t* __restrict__ hdrs, uint8_t* __restrict__ arenas,
+                                                                         uint64_t astride, uint32_t lit_cap, uint32_t seq_cap) {
+    __shared__ ZbWalkLds L;
+    __shared__ uint32_t sFail;
+    const uint32_t tid = threadIdx.x, lane = tid & (LANES - 1), b = blockIdx.x, chunk = blockIdx.y;
+    ZbChunk* const C = (ZbChunk*)(hdrs + (size_t)chunk * ZB_CHUNK_HDR_BYTES);
+    if (DUNI(ZB_LOAD_AGENT(&C->mode)) != 1) return;
+    const uint32_t nb = DUNI(C->nblocks);
+    if (b >= nb) return;
+    const tsx_chunk_desc d = descs[chunk];
+    const uint8_t* __restrict__ src = from_mid ? frames + (uint64_t)chunk * mid_stride : frames + d.src_off;
+    const ZbArena A = zb_arena(arenas, chunk, astride, lit_cap, seq_cap);
+    uint32_t* const words = A.words;
+    if (tid == 0) sFail = 0;
+    const ZbWalk w = zb_walk_to(L, C, nb, b, tid);
+    const uint32_t contentSize = DUNI(C->contentSize);
+    if (!w.ok || w.total != contentSize) { if (tid == 0) ZB_STORE_AGENT(&C->mode, 0u); return; }
+    const ZbBlock* const B = &C->blk[b];
+    const uint32_t btype = DUNI(B->btype), boff = DUNI(B->off);
+    if (b == 0 && tid == 0) descs[chunk].dst_len = contentSize;
+    if (btype == 0) { for (uint32_t i = tid; i < w.regen; i += ZB_SC_WAVES * LANES) words[w.start + i] = ZB_LIT | src[boff + i]; return; }
+    if (btype == 1) { const uint32_t v = ZB_LIT | src[boff]; for (uint32_t i = tid; i < w.regen; i += ZB_SC_WAVES * LANES) words[w.start + i] = v; return; }
+    const uint32_t res = zb_walk_block(L, B, src, A, seq_cap, w, tid, [words](uint32_t p, bool isLit, uint32_t v) { words[p] = isLit ? (ZB_LIT | v) : v; });
+    if (res == ZB_WALK_SUMS) { if (tid == 0) ZB_STORE_AGENT(&C->mode, 0u); return; }
+    if (res == ZB_WALK_REACH && lane == 0) sFail = 1;
     __threadfence_block();
     __syncthreads();
     if (tid == 0 && sFail) ZB_STORE_AGENT(&C->mode, 0u);                // the chunk-serial kernel behind this launch redoes the chunk
@@ -465,8 +497,9 @@ __global__ __launch_bounds__(ZB_SC_WAVES * LANES) void zb_scatter_kernel(const u
 // for every output position p, a literal byte equals orig[p] and a match byte satisfies orig[p - offset] == orig[p] - by induction
 // on p (the bytes before p are orig's, so the byte a match copies IS orig[p - offset]) that is byte equality of the restored chunk.
 // No order between sequences, blocks or workgroups, no word per output byte, no jump passes, no emit: this kernel runs behind
-// zb_index_kernel and zb_decode_kernel in place of zb_scatter_kernel, with that kernel's geometry and its prologue (kept as a copy of
-// its own: the fetch path's kernels stay the code they were) - and where scatter stores words[p], it compares.
+// zb_index_kernel and zb_decode_kernel in place of zb_scatter_kernel, with that kernel's geometry and ITS WALK (zb_walk_to,
+// zb_walk_block: a verdict is worth what its agreement with the reader's walk is, so there is one) - and where scatter stores
+// words[p], it compares.
 //
 // descs[i] describes FRAME i to the two kernels in front (src_len = frame bytes + 28, read with from_mid = 1; dst_cap = the source
 // chunk's length) and says where the source chunk is: src_base + dst_off.  status[i] != 0: chunk i is not verified.
@@ -483,11 +516,7 @@ __global__ __launch_bounds__(ZB_SC_WAVES * LANES) void zb_verify_kernel(const ui
                                                                         const tsx_chunk_desc* __restrict__ descs, const int32_t* __restrict__ status,
                                                                         const uint8_t* __restrict__ src_base, uint8_t* __restrict__ hdrs, uint8_t* __restrict__ arenas,
                                                                         uint64_t astride, uint32_t lit_cap, uint32_t seq_cap, uint32_t* __restrict__ verdicts) {
-    __shared__ uint32_t sRegen[ZB_MAX_BLOCKS];
-    __shared__ uint32_t sHist[3][ZB_MAX_BLOCKS];
-    __shared__ uint8_t sFlag[ZB_MAX_BLOCKS];
-    __shared__ uint32_t sLit[ZB_SC_GROUPS + 1], sTot[ZB_SC_GROUPS + 1];
-    __shared__ uint32_t gStart[ZB_SC_WAVES][LANES + 1], gLL[ZB_SC_WAVES][LANES], gLit[ZB_SC_WAVES][LANES], gSrc[ZB_SC_WAVES][LANES];
+    __shared__ ZbWalkLds L;
     const uint32_t tid = threadIdx.x, lane = tid & (LANES - 1), wv = DUNI(tid >> 6), b = blockIdx.x, chunk = blockIdx.y;
     if (status[chunk] != TSX_OK) return;
     ZbChunk* const C = (ZbChunk*)(hdrs + (size_t)chunk * ZB_CHUNK_HDR_BYTES);
@@ -522,110 +551,23 @@ __global__ __launch_bounds__(ZB_SC_WAVES * LANES) void zb_verify_kernel(const ui
     }
     const uint32_t nb = DUNI(C->nblocks);
     if (b >= nb) return;
-    const uint8_t* const litArena = arenas + (size_t)chunk * astride;
-    const uint32_t* const seqArena = (const uint32_t*)(litArena + lit_cap);
-    for (uint32_t i = tid; i < nb; i += ZB_SC_WAVES * LANES) {
-        const ZbBlock* const S = &C->blk[i];
-        sRegen[i] = S->regen;
-        sHist[0][i] = S->endHist[0]; sHist[1][i] = S->endHist[1]; sHist[2][i] = S->endHist[2];
-        sFlag[i] = (uint8_t)((S->btype == 2 ? 1 : 0) | (S->ok ? 2 : 0) | (S->nbSeq ? 4 : 0));
-    }
-    __threadfence_block();
-    __syncthreads();
-    uint32_t h0 = 1, h1 = 4, h2 = 8, myStart = 0, regen = 0;
-    {
-        uint32_t pos = 0; bool okAll = true;
-        for (uint32_t i = 0; i < nb; i++) {                             // wave-uniform; O(1) per block; every wave for itself
-            const uint32_t rg = DUNI(sRegen[i]), fl = DUNI(sFlag[i]);
-            if (i == b) { myStart = pos; regen = rg; }
-            if (fl & 1) {
-                if (!(fl & 2)) okAll = false;
-                if (i < b && (fl & 4)) {
-                    const uint32_t e0 = DUNI(sHist[0][i]), e1 = DUNI(sHist[1][i]), e2 = DUNI(sHist[2][i]);
-                    const uint32_t n0 = zb_subst(e0, h0, h1, h2), n1 = zb_subst(e1, h0, h1, h2), n2 = zb_subst(e2, h0, h1, h2);
-                    h0 = n0; h1 = n1; h2 = n2;
-                }
-            }
-            pos += rg;
-            if (pos > ZB_MAX_CHUNK) { okAll = false; break; }
-        }
-        // every workgroup of the chunk sees the same sums.  A block the decode kernel did not finish, or blocks that do not add up to the
-        // frame's own content size: a frame this form does not read - not taken.  A content size that is not the chunk's length: a mismatch
-        if (!okAll || pos != DUNI(C->contentSize)) { if (b == 0 && wv == 0) ZV_NOT_TAKEN(); return; }
-        if (pos != origLen) { if (b == 0 && wv == 0) ZV_FAIL(); return; }
-    }
+    const ZbWalk w = zb_walk_to(L, C, nb, b, tid);
+    // A block the decode kernel did not finish, or blocks that do not add up to the frame's own content size: a frame this form does
+    // not read - not taken.  A content size that is not the chunk's length: a mismatch
+    if (!w.ok || w.total != DUNI(C->contentSize)) { if (b == 0 && wv == 0) ZV_NOT_TAKEN(); return; }
+    if (w.total != origLen) { if (b == 0 && wv == 0) ZV_FAIL(); return; }
     if (b == 0 && tid == 0) V[ZB_V_SEEN] = 1;
-    // every position below is < origLen: the block's bytes are [myStart, myStart + regen) of a sum that equals it
+    // every position below is < origLen: the block's bytes are [w.start, w.start + w.regen) of a sum that equals it
     const ZbBlock* const B = &C->blk[b];
     const uint32_t btype = DUNI(B->btype), boff = DUNI(B->off);
     bool diff = false;
-    if (btype == 0) { for (uint32_t i = tid; i < regen; i += ZB_SC_WAVES * LANES) diff |= orig[myStart + i] != src[boff + i]; }
-    else if (btype == 1) { const uint8_t v = src[boff]; for (uint32_t i = tid; i < regen; i += ZB_SC_WAVES * LANES) diff |= orig[myStart + i] != v; }
+    if (btype == 0) { for (uint32_t i = tid; i < w.regen; i += ZB_SC_WAVES * LANES) diff |= orig[w.start + i] != src[boff + i]; }
+    else if (btype == 1) { const uint8_t v = src[boff]; for (uint32_t i = tid; i < w.regen; i += ZB_SC_WAVES * LANES) diff |= orig[w.start + i] != v; }
     else {
-        const uint32_t litSize = DUNI(B->litSize), nbSeq = DUNI(B->nbSeq);
-        const uint8_t* litPtr = litArena + DUNI(B->litAt);
-        if (DUNI(B->ltype) == 0) { const DecLit h = dec_lit_header(src + boff, DUNI(B->bsize)); litPtr = src + boff + h.hl; }
-        const uint32_t* const sLL = seqArena + DUNI(B->seqAt); const uint32_t* const sML = sLL + seq_cap; const uint32_t* const sOF = sML + seq_cap;
-        const uint32_t ngroups = (nbSeq + LANES - 1) / LANES;
-        if (ngroups > ZB_SC_GROUPS) { if (wv == 0) ZV_NOT_TAKEN(); return; }         // (the decode kernel bounds the match lengths' sum: cannot happen)
-        // sweep 1: the groups' byte counts
-        for (uint32_t gi = wv; gi < ngroups; gi += ZB_SC_WAVES) {
-            const uint32_t q = gi * LANES + lane;
-            uint32_t a = q < nbSeq ? sLL[q] : 0, t = q < nbSeq ? a + sML[q] : 0;
-            for (int o = 32; o; o >>= 1) { a += __shfl_xor(a, o); t += __shfl_xor(t, o); }
-            if (lane == 0) { sLit[gi] = a; sTot[gi] = t; }
-        }
-        __threadfence_block();
-        __syncthreads();
-        if (wv == 0) {                                                   // exclusive prefixes, 64 groups per step
-            uint32_t cl = 0, ct = 0;
-            for (uint32_t g0 = 0; g0 <= ngroups; g0 += LANES) {
-                const uint32_t gi = g0 + lane;
-                const uint32_t a = gi < ngroups ? sLit[gi] : 0, t = gi < ngroups ? sTot[gi] : 0;
-                uint32_t ia = a, it = t;
-                for (int o = 1; o < LANES; o <<= 1) {
-                    const uint32_t x = __shfl_up(ia, o), y = __shfl_up(it, o);
-                    if (lane >= (uint32_t)o) { ia += x; it += y; }
-                }
-                if (gi <= ngroups) { sLit[gi] = cl + ia - a; sTot[gi] = ct + it - t; }
-                cl += (uint32_t)__builtin_amdgcn_readlane(ia, LANES - 1); ct += (uint32_t)__builtin_amdgcn_readlane(it, LANES - 1);
-            }
-        }
-        __threadfence_block();
-        __syncthreads();
-        const uint32_t allLit = DUNI(sLit[ngroups]), allTot = DUNI(sTot[ngroups]);
-        if (allLit > litSize || allTot + (litSize - allLit) != regen) { if (wv == 0) ZV_NOT_TAKEN(); return; }    // (sums the decode kernel has checked)
-        // sweep 2: every group on its own
-        for (uint32_t gi = wv; gi < ngroups; gi += ZB_SC_WAVES) {
-            const uint32_t g = gi * LANES;
-            const uint32_t cnt = nbSeq - g < LANES ? nbSeq - g : LANES;
-            const uint32_t lp = DUNI(sLit[gi]), opos = myStart + DUNI(sTot[gi]), groupTot = DUNI(sTot[gi + 1]) - DUNI(sTot[gi]);
-            const bool valid = lane < cnt;
-            const uint32_t ll = valid ? sLL[g + lane] : 0, ml = valid ? sML[g + lane] : 0;
-            uint32_t off = valid ? sOF[g + lane] : 0;
-            if (off & ZB_SYM) off = zb_subst(off, h0, h1, h2);
-            uint32_t litIncl = ll, totIncl = ll + ml;
-            for (int o = 1; o < LANES; o <<= 1) {
-                const uint32_t a = __shfl_up(litIncl, o), t = __shfl_up(totIncl, o);
-                if (lane >= (uint32_t)o) { litIncl += a; totIncl += t; }
-            }
-            const uint32_t myLit = lp + litIncl - ll, myOut = opos + totIncl - (ll + ml), mOut = myOut + ll;
-            if (__any(valid && ml && (off == 0 || off > mOut))) { diff = true; break; }       // a match that starts before the chunk does: restores nothing
-            WAVE_SYNC();
-            gStart[wv][lane] = valid ? myOut : opos + groupTot; gLL[wv][lane] = ll; gLit[wv][lane] = myLit; gSrc[wv][lane] = mOut - off;
-            if (lane == 0) gStart[wv][LANES] = opos + groupTot;
-            __threadfence_block();
-            WAVE_SYNC();
-            for (uint32_t p = opos + lane; p < opos + groupTot; p += LANES) {
-                uint32_t i = 0;
-                for (uint32_t s_ = 32; s_; s_ >>= 1) if (gStart[wv][i + s_] <= p) i += s_;     // the last sequence that starts at or before p
-                const uint32_t rel = p - gStart[wv][i], l_ = gLL[wv][i];
-                const uint8_t want = rel < l_ ? litPtr[gLit[wv][i] + rel] : orig[gSrc[wv][i] + (rel - l_)];    // (the source of a match byte is < p)
-                diff |= orig[p] != want;
-            }
-        }
-        // the literals behind the last sequence
-        for (uint32_t k = tid; k < litSize - allLit; k += ZB_SC_WAVES * LANES) diff |= orig[myStart + allTot + k] != litPtr[allLit + k];
+        const uint32_t res = zb_walk_block(L, B, src, zb_arena(arenas, chunk, astride, lit_cap, seq_cap), seq_cap, w, tid,
+                                           [orig, &diff](uint32_t p, bool isLit, uint32_t v) { diff |= orig[p] != (isLit ? (uint8_t)v : orig[v]); });
+        if (res == ZB_WALK_SUMS) { if (wv == 0) ZV_NOT_TAKEN(); return; }
+        diff |= res == ZB_WALK_REACH;                                   // a match that starts before the chunk does: restores nothing
     }
     if (__any(diff)) ZV_FAIL();
     // Four wrong checksum bytes make a chunk unreadable to every reader: the last wave of the frame's last block (the short one) hashes the
@@ -654,7 +596,7 @@ __global__ __launch_bounds__(256) void zb_jump_kernel(uint8_t* __restrict__ hdrs
     if (round > 0 && C->live[round - 1] == 0) return;
     const uint32_t n = C->contentSize, p = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (p >= n) return;
-    uint32_t* const words = (uint32_t*)(arenas + (size_t)chunk * astride + lit_cap + 12u * (size_t)seq_cap);
+    uint32_t* const words = zb_arena(arenas, chunk, astride, lit_cap, seq_cap).words;
     const uint32_t* rd = words;                                         // what this pass reads (the array itself: the update is in place)
 #ifdef HIPEMU
     if (g_zb_snap) rd = (const uint32_t*)(g_zb_snap + ((const uint8_t*)words - arenas));
@@ -692,7 +634,7 @@ __global__ __launch_bounds__(256) void zb_emit_kernel(const tsx_chunk_desc* __re
     if (C->mode != 1) return;
     const uint32_t n = C->contentSize, p = (blockIdx.x * 256 + threadIdx.x) * 16, lane = threadIdx.x & (LANES - 1);
     if (p - lane * 16 >= n) return;                                     // whole waves leave: the lanes of a wave with bytes stay together for the hand-off below
-    const uint32_t* const words = (const uint32_t*)(arenas + (size_t)chunk * astride + lit_cap + 12u * (size_t)seq_cap);
+    const uint32_t* const words = zb_arena(arenas, chunk, astride, lit_cap, seq_cap).words;
     uint8_t* const out = dst_base + descs[chunk].dst_off;                // slots are 16-byte aligned
     uint32_t all = ZB_LIT;
     if (p >= n) {}
@@ -725,10 +667,14 @@ __global__ __launch_bounds__(256) void zb_emit_kernel(const tsx_chunk_desc* __re
 // ---------------------------------------------------------------------------------------------------
 static inline uint32_t zb_lit_cap(uint32_t max_out) { return ((max_out + 80u * ZB_MAX_BLOCKS) + 255u) & ~255u; }
 static inline uint32_t zb_seq_cap(uint32_t max_out) { return ((max_out / 3u + 64u * ZB_MAX_BLOCKS + 64u) + 63u) & ~63u; }
-static inline size_t zb_arena_stride(uint32_t max_out) {
-    return ((size_t)zb_lit_cap(max_out) + 12u * (size_t)zb_seq_cap(max_out) + 4u * ((size_t)max_out + 64u) + 255u) & ~(size_t)255u;
+static inline size_t zb_align256(size_t v) { return (v + 255u) & ~(size_t)255u; }
+static inline size_t zb_verify_stride(uint32_t max_out) { return zb_align256(zb_arena_words_at(zb_lit_cap(max_out), zb_seq_cap(max_out))); }
+static inline size_t zb_arena_stride(uint32_t max_out) { return zb_align256(zb_arena_words_at(zb_lit_cap(max_out), zb_seq_cap(max_out)) + 4u * ((size_t)max_out + 64u)); }
+// workspace of a batch: [n chunk headers][n arenas]
+struct ZbWork { uint8_t* hdrs; uint8_t* arenas; uint64_t astride; uint32_t lit_cap, seq_cap; };
+static inline ZbWork zb_work(void* work, uint32_t n, uint32_t max_out, size_t astride) {
+    return ZbWork{(uint8_t*)work, (uint8_t*)work + (size_t)n * ZB_CHUNK_HDR_BYTES, (uint64_t)astride, zb_lit_cap(max_out), zb_seq_cap(max_out)};
 }
-// workspace of a batch: [n chunk headers][n arenas: literals | literal lengths | match lengths | offsets | one word per output byte]
 size_t tsx_zstd_blockmode_bytes(uint32_t n, uint32_t max_out) { return (size_t)n * (ZB_CHUNK_HDR_BYTES + zb_arena_stride(max_out)); }
 bool tsx_zstd_blockmode_takes(uint32_t max_out) { return max_out <= ZB_MAX_CHUNK; }
 // the list zstd_decompress_kernel skips by: word i * stride == 1 <=> chunk i was decoded here
@@ -737,20 +683,23 @@ const uint32_t* tsx_zstd_blockmode_skip(const void* bwork, uint32_t* stride_word
     return (const uint32_t*)((const uint8_t*)bwork + offsetof(ZbChunk, mode));
 }
 
+// index + decode: the two launches in front of scatter and of verify (zbprof: the phase laps' buffer of a TSX_PROF2 build, or null)
+static void zb_launch_index_decode(hipStream_t st, const uint8_t* frames, int from_mid, uint64_t mid_stride, const tsx_chunk_desc* d_descs,
+                                   const int32_t* d_status, uint32_t n, const ZbWork& W, unsigned long long* zbprof) {
+    hipLaunchKernelGGL(zb_index_kernel, dim3(n), dim3(LANES), 0, st, frames, from_mid, mid_stride, d_descs, d_status, W.hdrs, W.lit_cap, W.seq_cap);
+    hipLaunchKernelGGL(zb_decode_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(2 * LANES), 0, st, frames, from_mid, mid_stride, d_descs, W.hdrs, W.arenas, W.astride, W.lit_cap, W.seq_cap
+#ifdef TSX_PROF2
+                       , zbprof
+#endif
+                       );
+}
+
 uint32_t tsx_launch_zstd_decompress_blocks(hipStream_t st, const uint8_t* frames, int from_mid, uint64_t mid_stride, tsx_chunk_desc* d_descs, uint32_t n,
                                            uint32_t max_out, uint8_t* dst, int32_t* d_status, void* bwork) {
     if (!n) return 0;
-    uint8_t* const hdrs = (uint8_t*)bwork;
-    uint8_t* const arenas = hdrs + (size_t)n * ZB_CHUNK_HDR_BYTES;
-    const size_t astride = zb_arena_stride(max_out);
-    const uint32_t lit_cap = zb_lit_cap(max_out), seq_cap = zb_seq_cap(max_out);
-    hipLaunchKernelGGL(zb_index_kernel, dim3(n), dim3(LANES), 0, st, frames, from_mid, mid_stride, (const tsx_chunk_desc*)d_descs, (const int32_t*)d_status, hdrs, lit_cap, seq_cap);
-    hipLaunchKernelGGL(zb_decode_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(2 * LANES), 0, st, frames, from_mid, mid_stride, (const tsx_chunk_desc*)d_descs, hdrs, arenas, (uint64_t)astride, lit_cap, seq_cap
-#ifdef TSX_PROF2
-                       , g_zbprof_out
-#endif
-                       );
-    hipLaunchKernelGGL(zb_scatter_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(ZB_SC_WAVES * LANES), 0, st, frames, from_mid, mid_stride, d_descs, hdrs, arenas, (uint64_t)astride, lit_cap, seq_cap);
+    const ZbWork W = zb_work(bwork, n, max_out, zb_arena_stride(max_out));
+    zb_launch_index_decode(st, frames, from_mid, mid_stride, d_descs, d_status, n, W, ZB_PROF_OUT);
+    hipLaunchKernelGGL(zb_scatter_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(ZB_SC_WAVES * LANES), 0, st, frames, from_mid, mid_stride, d_descs, W.hdrs, W.arenas, W.astride, W.lit_cap, W.seq_cap);
     // A copy chain is at most as long as the chunk.  A pass makes two jumps IN PLACE: the first reads its source's word, the second the
     // word of what that named - either may still hold its value from before the pass (another thread has not stored yet), so what a pass
     // guarantees is old[old[old[q]]]: three hops of the chain as it was, not four.  ceil(log3(max_out)) + 1 passes therefore resolve every
@@ -763,45 +712,33 @@ uint32_t tsx_launch_zstd_decompress_blocks(hipStream_t st, const uint8_t* frames
 #ifdef HIPEMU
     // test harness: TSX_EMU_JUMP_SNAPSHOT=1 gives every pass the word array as it was before the pass (the worst store order),
     // TSX_EMU_JUMP_ROUNDS=k queues k passes instead of the bound above (to show what too few do)
-    uint8_t* snap = getenv("TSX_EMU_JUMP_SNAPSHOT") ? (uint8_t*)malloc((size_t)n * astride) : nullptr;
+    uint8_t* snap = getenv("TSX_EMU_JUMP_SNAPSHOT") ? (uint8_t*)malloc((size_t)n * W.astride) : nullptr;
     if (const char* e = getenv("TSX_EMU_JUMP_ROUNDS")) { const long v = atol(e); if (v >= 1 && v <= 31) rounds = (uint32_t)v; }
 #endif
     for (uint32_t r = 0; r < rounds; r++) {
 #ifdef HIPEMU
-        if (snap) { memcpy(snap, arenas, (size_t)n * astride); g_zb_snap = snap; }
+        if (snap) { memcpy(snap, W.arenas, (size_t)n * W.astride); g_zb_snap = snap; }
 #endif
-        hipLaunchKernelGGL(zb_jump_kernel, dim3(tiles, n), dim3(256), 0, st, hdrs, arenas, (uint64_t)astride, lit_cap, seq_cap, r);
+        hipLaunchKernelGGL(zb_jump_kernel, dim3(tiles, n), dim3(256), 0, st, W.hdrs, W.arenas, W.astride, W.lit_cap, W.seq_cap, r);
     }
 #ifdef HIPEMU
     if (snap) { g_zb_snap = nullptr; free(snap); }                     // (snapshot mode is a single-threaded test: callers without it never touch the word)
 #endif
-    hipLaunchKernelGGL(zb_emit_kernel, dim3((max_out + 4095) / 4096, n), dim3(256), 0, st, (const tsx_chunk_desc*)d_descs, dst, hdrs, arenas, (uint64_t)astride, lit_cap, seq_cap);
+    hipLaunchKernelGGL(zb_emit_kernel, dim3((max_out + 4095) / 4096, n), dim3(256), 0, st, (const tsx_chunk_desc*)d_descs, dst, W.hdrs, W.arenas, W.astride, W.lit_cap, W.seq_cap);
     return 4 + rounds;
 }
 
 // ---- verify on upload --------------------------------------------------------------------------------
-// index, decode, verify: three launches.  The workspace is the decoder's without its largest part, the word per output byte:
-// [n chunk headers][n arenas: literals | literal lengths | match lengths | offsets].  max_len: the longest source chunk of the launch
-// (chunks above ZB_MAX_CHUNK are not taken; the arenas are sized for the others).
+// index, decode, verify: three launches.  The workspace is the decoder's without its largest part, the word per output byte.
+// max_len: the longest source chunk of the launch (chunks above ZB_MAX_CHUNK are not taken; the arenas are sized for the others).
 static inline uint32_t zb_verify_max(uint32_t max_len) { return max_len < ZB_MAX_CHUNK ? max_len : ZB_MAX_CHUNK; }
-static inline size_t zb_verify_stride(uint32_t max_len) {
-    return ((size_t)zb_lit_cap(zb_verify_max(max_len)) + 12u * (size_t)zb_seq_cap(zb_verify_max(max_len)) + 255u) & ~(size_t)255u;
-}
-size_t tsx_zstd_verify_bytes(uint32_t n, uint32_t max_len) { return (size_t)n * (ZB_CHUNK_HDR_BYTES + zb_verify_stride(max_len)); }
+size_t tsx_zstd_verify_bytes(uint32_t n, uint32_t max_len) { return (size_t)n * (ZB_CHUNK_HDR_BYTES + zb_verify_stride(zb_verify_max(max_len))); }
 uint32_t tsx_launch_zstd_verify_blocks(hipStream_t st, const uint8_t* frames, uint64_t mid_stride, const tsx_chunk_desc* d_descs, const int32_t* d_status,
                                        uint32_t n, uint32_t max_len, const uint8_t* src_base, void* work, uint32_t* verdicts) {
     if (!n) return 0;
-    uint8_t* const hdrs = (uint8_t*)work;
-    uint8_t* const arenas = hdrs + (size_t)n * ZB_CHUNK_HDR_BYTES;
-    const size_t astride = zb_verify_stride(max_len);
-    const uint32_t lit_cap = zb_lit_cap(zb_verify_max(max_len)), seq_cap = zb_seq_cap(zb_verify_max(max_len));
-    hipLaunchKernelGGL(zb_index_kernel, dim3(n), dim3(LANES), 0, st, frames, 1, mid_stride, d_descs, d_status, hdrs, lit_cap, seq_cap);
-    hipLaunchKernelGGL(zb_decode_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(2 * LANES), 0, st, frames, 1, mid_stride, d_descs, hdrs, arenas, (uint64_t)astride, lit_cap, seq_cap
-#ifdef TSX_PROF2
-                       , (unsigned long long*)nullptr
-#endif
-                       );
-    hipLaunchKernelGGL(zb_verify_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(ZB_SC_WAVES * LANES), 0, st, frames, mid_stride, d_descs, d_status, src_base, hdrs, arenas,
-                       (uint64_t)astride, lit_cap, seq_cap, verdicts);
+    const ZbWork W = zb_work(work, n, zb_verify_max(max_len), zb_verify_stride(zb_verify_max(max_len)));
+    zb_launch_index_decode(st, frames, 1, mid_stride, d_descs, d_status, n, W, nullptr);
+    hipLaunchKernelGGL(zb_verify_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(ZB_SC_WAVES * LANES), 0, st, frames, mid_stride, d_descs, d_status, src_base, W.hdrs, W.arenas,
+                       W.astride, W.lit_cap, W.seq_cap, verdicts);
     return 3;
 }
