@@ -202,3 +202,29 @@ def window_edge_case(seed):
 
 def window_edge_cases():
     return [window_edge_case(s) for s in WINDOW_EDGE_SEEDS]
+
+
+def header_cases():
+    """tests/golden/fuzz_regress/hdr_*.bin, by name: the smallest inputs whose level-3 frames carry the literal-section headers no other case
+    of the differential tests produces.  No RNG: incompressible bytes come from SHA-256 in counter mode.
+      hdr_lit_raw_31 / 32 / 33   n noise bytes, then nine copies: n raw literals and one match - the 1-byte header ends at 31
+      hdr_lit_raw_4095 / 4096    the same with one copy: the 2-byte header ends at 4095
+      hdr_lit_rle_70             RLE literals in a compressed block.  Every literal of the block must be the same byte, and a frame's first bytes
+                                 are literals of whatever they are, so it takes a SECOND block, i.e. a first one of 128 KiB: 200-byte noise
+                                 segments, each closed by an 8-byte marker (a match every 208 bytes keeps the parser visiting every position);
+                                 then seventy times one byte 0xA5 and 32 bytes from the middle of a segment - seventy equal literals between
+                                 seventy matches.  133 382 bytes: no shorter input has a second block."""
+    import hashlib
+    noise = np.frombuffer(b"".join(hashlib.sha256(b"tsx header cases %d" % i).digest() for i in range(4200)), np.uint8)
+    c = {}
+    for n in (31, 32, 33):
+        c["hdr_lit_raw_%d" % n] = np.tile(noise[:n], 10)
+    for n in (4095, 4096):
+        c["hdr_lit_raw_%d" % n] = np.concatenate([noise[:n], noise[:n]])
+    marker = np.frombuffer(b"~marker~", np.uint8)
+    segs = [noise[200 * j:200 * j + 200] for j in range(640)]
+    parts = [np.concatenate([np.concatenate([s, marker]) for s in segs])[:BLOCK]]
+    for j in range(5, 355, 5):
+        parts += [np.array([0xA5], np.uint8), segs[j][60:92]]
+    c["hdr_lit_rle_70"] = np.concatenate(parts)
+    return c

@@ -22,7 +22,7 @@ def source_sha(names):
     return h.hexdigest()[:16]
 
 
-ENC_SOURCES = ["zstd_enc.hip", "svc_dev.h", "zstd_common.h", "gcm_dev.h", "crc_dev.h"]
+ENC_SOURCES = ["zstd_enc.hip", "zstd_enc_dev.h", "zstd_enc_parse.h", "zstd_enc_huf.h", "zstd_enc_entropy.h", "svc_dev.h", "zstd_common.h", "gcm_dev.h", "crc_dev.h"]
 CRC_SOURCES = ["crc32c.hip", "crc_dev.h"]
 GCM_SOURCES = ["gcm.hip", "gcm_dev.h"]
 DEC_SOURCES = ["zstd_dec.hip", "zstd_dec_dev.h", "zstd_common.h"]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase profile of zstd_compress_kernel (libtsxform_prof.so, `make -C csrc prof`): s_memtime lap timers per chunk.
+"""Phase profile of zstd_service_kernel (libtsxform_prof.so, `make -C csrc prof`): s_memtime lap timers per chunk.
 Usage (GPU box): python tools/prof_zstd.py [--chunks 2048] [--dist K] -> JSON with mean cycles per bucket."""
 import argparse
 import ctypes as C

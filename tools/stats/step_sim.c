@@ -1,7 +1,7 @@
 /* Wave-step model of the GPU parser over the exact level-3 parse of a chunk (analysis tool, not product code).
  *
  * The serial restatement (oracle/zstd_l3.c, ORC_TRACE hooks on) yields the table-access trace of the parse: search runs, visited
- * positions, events, complementary insertions.  That trace is replayed through a model of csrc/zstd_enc.hip's match_block2:
+ * positions, events, complementary insertions.  That trace is replayed through a model of csrc/zstd_enc_parse.h's match_block:
  *   - a step probes K consecutive positions (schedule K0, K1, then doubling to 59), 2 table reads per position + 1 look-ahead;
  *   - an optional per-chunk SLOT CACHE in LDS (direct mapped, write back, exact): insertions of recurring content land there,
  *     a probe that hits needs no global read, and the first lane of a step that hits ends the step's speculation (it is almost
