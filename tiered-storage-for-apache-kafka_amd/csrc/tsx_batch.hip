@@ -446,7 +446,7 @@ static int verify_piece(tsx_run& r, const tsx_sub& sb, bool self_status, int32_t
             if (grc) { (void)hipGetLastError(); continue; }            // vcode[j] stays TSX_E_NOMEM
             W[ZB_V_FAIL] = 0; W[ZB_V_NOT_TAKEN] = 0; W[ZB_V_SEEN] = 0;
             HIPCHK(hipEventRecord(c->ev[EV_VERIFY_BEGIN], c->st));
-            t.unzstd_launches += 1 + tsx_launch_zstd_decompress(c->st, dev->d_zc, c->d_mid + (size_t)j * c->mid_stride, 1, (uint64_t)c->mid_stride, fdescs + i, 1, V->full, fstatus + i,
+            t.unzstd_launches += 1 + tsx_launch_zstd_decompress(c->st, c->d_mid + (size_t)j * c->mid_stride, 1, (uint64_t)c->mid_stride, fdescs + i, 1, V->full, fstatus + i,
                                                                 (uint8_t*)c->d_zwork + (size_t)j * tsx_zstd_workspace_bytes(1, 0), nullptr, 0, true);
             const uint32_t blocks = std::max(1u, std::min(1024u, r.descs[j].src_len / 4096u));
             hipLaunchKernelGGL(verify_compare_kernel, dim3(blocks), dim3(256), 0, c->st, (const uint8_t*)V->full, r.d_src + r.descs[j].src_off, (const tsx_chunk_desc*)(fdescs + i),
@@ -700,7 +700,7 @@ static int launch_stages(const tsx_run& r, const tsx_sub& sb, hipEvent_t* e, hip
             //  waits for the compressor service's kernel - and its scratch - to go away)
             bool busy_service = false;
             if (!skip) busy_service = svc_busy(c->dev);
-            t.unzstd_launches += tsx_launch_zstd_decompress(st, c->dev->d_zc, zsrc, r.enc ? 1 : 0, (uint64_t)c->mid_stride, dd, n, r.d_dst, ds, dzw, skip, skip_stride, busy_service);
+            t.unzstd_launches += tsx_launch_zstd_decompress(st, zsrc, r.enc ? 1 : 0, (uint64_t)c->mid_stride, dd, n, r.d_dst, ds, dzw, skip, skip_stride, busy_service);
         } else if (!r.enc) launch_copy_chunks(r, st, lo, n, 0, r.d_src);
         hipLaunchKernelGGL(publish_status_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dd, (const int32_t*)ds, n, hm);
         if (r.enc && !r.comp) launch_scrub_failed(r, st, lo, n);   // decrypted straight into the caller's slots: nothing of a chunk that failed its tag check stays

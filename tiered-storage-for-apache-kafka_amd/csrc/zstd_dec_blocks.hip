@@ -185,28 +185,18 @@ __global__ __launch_bounds__(LANES) void zb_index_kernel(const uint8_t* __restri
 // decode: one workgroup (wave 0 sequences, wave 1 literals) per block
 // ---------------------------------------------------------------------------------------------------
 #define ZB_FAIL() do { if (lane == 0) ZB_STORE_AGENT(&C->mode, 0u); return; } while (0)
+static DecLapOut g_zbprof_out;                                        // 8 u64 per (chunk, block): phase laps of zb_decode_kernel (tools/zb_phase_laps.py)
 #ifdef TSX_PROF2
-static unsigned long long* g_zbprof_out = nullptr;                    // 8 u64 per (chunk, block): phase laps of zb_decode_kernel (tools/zb_phase_laps.py)
-extern "C" void tsx_debug_set_zbprof(void* dev_ptr) { g_zbprof_out = (unsigned long long*)dev_ptr; }
-#define ZLT(k) do { const unsigned long long n_ = (unsigned long long)clock64(); zlt_[k] += n_ - zlast_; zlast_ = n_; } while (0)
-#define ZB_PROF_OUT g_zbprof_out
-#else
-#define ZB_PROF_OUT ((unsigned long long*)nullptr)
-#define ZLT(k) do {} while (0)
+extern "C" void tsx_debug_set_zbprof(void* dev_ptr) { g_zbprof_out.buf = (unsigned long long*)dev_ptr; }
 #endif
 
 __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __restrict__ frames, int from_mid, uint64_t mid_stride,
                                                               const tsx_chunk_desc* __restrict__ descs, uint8_t* __restrict__ hdrs, uint8_t* __restrict__ arenas,
-                                                              uint64_t astride, uint32_t lit_cap, uint32_t seq_cap
-#ifdef TSX_PROF2
-                                                              , unsigned long long* __restrict__ zbprof
-#endif
-                                                              ) {
+                                                              uint64_t astride, uint32_t lit_cap, uint32_t seq_cap, DecLapOut zbprof) {
     __shared__ DecLds L;
     const uint32_t lane = threadIdx.x & (LANES - 1), role = DUNI(threadIdx.x >> 6), b = blockIdx.x, chunk = blockIdx.y;
-#ifdef TSX_PROF2
-    unsigned long long zlt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, zlast_ = (unsigned long long)clock64();
-#endif
+    DecLaps laps;
+    const size_t lapRow = (size_t)chunk * ZB_MAX_BLOCKS + b;
     ZbChunk* const C = (ZbChunk*)(hdrs + (size_t)chunk * ZB_CHUNK_HDR_BYTES);
     if (DUNI(C->mode) != 1 || b >= DUNI(C->nblocks)) return;
     ZbBlock* const B = &C->blk[b];
@@ -231,32 +221,20 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
             if (sh.ltype != 2 || !sh.section) ZB_FAIL();
             tree = sblk + sh.hl; treeAvail = sh.csize;
         }
-        if (lane == 0) { L.hufValid = 0; L.scalH[0] = huf_readTable(L, tree, treeAvail); }
-        __threadfence_block();
-        WAVE_SYNC();
-        const uint32_t used = DUNI(L.scalH[0]);
-        WAVE_SYNC();
+        const uint32_t used = dec_huf_tree(L, tree, treeAvail, lane);
         if (!used) ZB_FAIL();
-        huf_buildX_wave(L, lane);
-        __threadfence_block();
-        WAVE_SYNC();
-        ZLT(6);
+        laps.lap(6);
         if (h.ltype == 2) t += used;
         if (t > h.hl + h.csize) ZB_FAIL();
         if (!dec_huf_streams(L, blk + t, h.hl + h.csize - t, h.streams, h.litSize, lit, lane)) ZB_FAIL();
-        ZLT(7);
-#ifdef TSX_PROF2
-        if (lane == 0 && zbprof) { unsigned long long* const zp = zbprof + ((size_t)chunk * ZB_MAX_BLOCKS + b) * 8; zp[6] = zlt_[6]; zp[7] = zlt_[7]; }
-#endif
+        laps.lap(7);
+        if (lane == 0) { laps.put(zbprof, lapRow, 6, 6); laps.put(zbprof, lapRow, 7, 7); }
         return;
     }
     // ---- sequences ----
     const uint32_t nbSeq = DUNI(B->nbSeq), litSize = DUNI(B->litSize);
     if (nbSeq == 0) { if (lane == 0) { B->regen = litSize; B->endHist[0] = ZB_SYM; B->endHist[1] = ZB_SYM | (1u << 28); B->endHist[2] = ZB_SYM | (2u << 28); B->ok = 1; } return; }
-    if (lane == 0) L.zeroEntry = 0;
-    if (lane < 36) { L.cLLbase[lane] = dLLbase[lane]; L.cLLbits[lane] = dLLbits[lane]; }
-    if (lane < 53) { L.cMLbase[lane] = dMLbase[lane]; L.cMLbits[lane] = dMLbits[lane]; }
-    __threadfence_block();
+    dec_code_tables(L, lane);
     WAVE_SYNC();
     for (int k = 0; k < 3; k++) {
         const ZbBlock* const S = &C->blk[DUNI(B->tblSrc[k])];           // this block itself unless the table is a Repeat
@@ -264,7 +242,7 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
         if (mode == 3 || to > sb) ZB_FAIL();
         if (dec_seq_table(L, k, mode, src + DUNI(S->off) + to, sb - to, lane) < 0) ZB_FAIL();
     }
-    ZLT(0);
+    laps.lap(0);
     uint32_t* const sLL = A.seq + DUNI(B->seqAt); uint32_t* const sML = sLL + seq_cap; uint32_t* const sOF = sML + seq_cap;
     const uint32_t t = DUNI(B->streamOff);
     DecSeqStream stream = {blk + t, bsize - t, 0, 0, 0};                // n >= 1 (index kernel)
@@ -275,48 +253,19 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
         uint32_t ll, ml, offBase;
         if (!dec_seq_group(L, stream, g, cnt, nbSeq, lane, ll, ml, offBase)) ZB_FAIL();
         const bool valid = lane < cnt;
-        ZLT(1);
+        laps.lap(1);
         if (__any(valid && offBase > 3 && offBase - 3 >= ZB_SYM)) ZB_FAIL();     // an offset of 2 GiB or more: not in a frame this form takes
         // pass 3: repeat offsets, on values that are either offsets or references into the incoming history
-        uint32_t off = offBase - 3;
-        {
-            const unsigned long long ll0 = __ballot(valid && ll == 0);
-            unsigned long long users = __ballot(valid && offBase <= 3);
-            uint32_t prev = 0;
-            for (;;) {
-                const uint32_t j = users ? (uint32_t)__ffsll((long long)users) - 1 : cnt;
-                const uint32_t gap = j - prev;
-                const uint32_t a1 = __builtin_amdgcn_readlane(offBase, (int)(j >= 1 ? j - 1 : 0)) - 3;
-                const uint32_t a2 = __builtin_amdgcn_readlane(offBase, (int)(j >= 2 ? j - 2 : 0)) - 3;
-                const uint32_t a3 = __builtin_amdgcn_readlane(offBase, (int)(j >= 3 ? j - 3 : 0)) - 3;
-                const uint32_t n2 = gap >= 3 ? a3 : gap == 2 ? r0 : gap == 1 ? r1 : r2;
-                const uint32_t n1 = gap >= 2 ? a2 : gap == 1 ? r0 : r1;
-                const uint32_t n0 = gap >= 1 ? a1 : r0;
-                r0 = n0; r1 = n1; r2 = n2;
-                if (!users) break;
-                users &= users - 1;
-                const uint32_t ob = __builtin_amdgcn_readlane(offBase, (int)j);
-                const uint32_t idx = ob - 1 + (uint32_t)((ll0 >> j) & 1);
-                const uint32_t c01 = idx == 0 ? r0 : r1, c23 = idx == 2 ? r2 : zb_sym_dec(r0);
-                const uint32_t o_ = idx < 2 ? c01 : c23;
-                r2 = idx >= 2 ? r1 : r2;
-                r1 = idx >= 1 ? r0 : r1;
-                r0 = o_;
-                off = tsx_writelane(o_, j, off);
-                prev = j + 1;
-            }
-        }
-        ZLT(4);
+        const uint32_t off = dec_rep_offsets(offBase, ll, valid, cnt, r0, r1, r2, [](uint32_t v) { return zb_sym_dec(v); });
+        laps.lap(4);
         if (valid) { sLL[g + lane] = ll; sML[g + lane] = ml; sOF[g + lane] = off; }
         uint32_t a = ll, m = ml;
         for (int o = 32; o; o >>= 1) { a += __shfl_xor(a, o); m += __shfl_xor(m, o); }
         sumLL += DUNI(a); sumML += DUNI(m);
         if (sumLL > litSize || litSize + sumML > ZS_BLOCK_MAX) ZB_FAIL();   // a block regenerates at most Block_Maximum_Size bytes
-        ZLT(5);
+        laps.lap(5);
     }
-#ifdef TSX_PROF2
-    if (lane == 0 && zbprof) { unsigned long long* const zp = zbprof + ((size_t)chunk * ZB_MAX_BLOCKS + b) * 8; for (int k = 0; k < 6; k++) zp[k] = zlt_[k]; }
-#endif
+    if (lane == 0) for (int k = 0; k < 6; k++) laps.put(zbprof, lapRow, k, k);
     if (stream.B != 0) ZB_FAIL();                                       // every bit of the stream was used
     if (lane == 0) { B->regen = litSize + sumML; B->endHist[0] = r0; B->endHist[1] = r1; B->endHist[2] = r2; B->ok = 1; }
 }
@@ -335,10 +284,6 @@ __global__ __launch_bounds__(2 * LANES) void zb_decode_kernel(const uint8_t* __r
 // holds either ancestor - both are valid - so the update is done in place).
 // ---------------------------------------------------------------------------------------------------
 #define ZB_LIT 0x80000000u                      /* src word: ZB_LIT | byte (resolved), else the chunk position this byte copies from */
-
-__device__ __forceinline__ static void zb_incl_scan2(uint32_t& a, uint32_t& t, uint32_t lane) {      // inclusive scan of two values over the wave
-    for (int o = 1; o < LANES; o <<= 1) { const uint32_t x = __shfl_up(a, o), y = __shfl_up(t, o); if (lane >= (uint32_t)o) { a += x; t += y; } }
-}
 
 // ---- the block walk: what zb_scatter_kernel and zb_verify_kernel share ----
 // One workgroup of ZB_SC_WAVES waves per block.  Every wave walks the block summaries (positions, incoming repeat-offset history:
@@ -416,7 +361,7 @@ __device__ __forceinline__ static uint32_t zb_walk_block(ZbWalkLds& L, const ZbB
             const uint32_t gi = g0 + lane;
             const uint32_t a = gi < ngroups ? L.lit[gi] : 0, t = gi < ngroups ? L.tot[gi] : 0;
             uint32_t ia = a, it = t;
-            zb_incl_scan2(ia, it, lane);
+            dec_incl_scan2(ia, it, lane);
             if (gi <= ngroups) { L.lit[gi] = cl + ia - a; L.tot[gi] = ct + it - t; }
             cl += (uint32_t)__builtin_amdgcn_readlane(ia, LANES - 1); ct += (uint32_t)__builtin_amdgcn_readlane(it, LANES - 1);
         }
@@ -436,7 +381,7 @@ __device__ __forceinline__ static uint32_t zb_walk_block(ZbWalkLds& L, const ZbB
         uint32_t off = valid ? sOF[g + lane] : 0;
         if (off & ZB_SYM) off = zb_subst(off, w.h0, w.h1, w.h2);
         uint32_t litIncl = ll, totIncl = ll + ml;
-        zb_incl_scan2(litIncl, totIncl, lane);
+        dec_incl_scan2(litIncl, totIncl, lane);
         const uint32_t myLit = lp + litIncl - ll, myOut = opos + totIncl - (ll + ml), mOut = myOut + ll;
         if (__any(valid && ml && (off == 0 || off > mOut))) { res = ZB_WALK_REACH; break; }
         // the group's ~1.5 KB of output, all lanes side by side: position -> its sequence by a binary search over the 64 start
@@ -683,22 +628,18 @@ const uint32_t* tsx_zstd_blockmode_skip(const void* bwork, uint32_t* stride_word
     return (const uint32_t*)((const uint8_t*)bwork + offsetof(ZbChunk, mode));
 }
 
-// index + decode: the two launches in front of scatter and of verify (zbprof: the phase laps' buffer of a TSX_PROF2 build, or null)
+// index + decode: the two launches in front of scatter and of verify (zbprof: where a TSX_PROF2 build leaves the phase laps, if anywhere)
 static void zb_launch_index_decode(hipStream_t st, const uint8_t* frames, int from_mid, uint64_t mid_stride, const tsx_chunk_desc* d_descs,
-                                   const int32_t* d_status, uint32_t n, const ZbWork& W, unsigned long long* zbprof) {
+                                   const int32_t* d_status, uint32_t n, const ZbWork& W, DecLapOut zbprof) {
     hipLaunchKernelGGL(zb_index_kernel, dim3(n), dim3(LANES), 0, st, frames, from_mid, mid_stride, d_descs, d_status, W.hdrs, W.lit_cap, W.seq_cap);
-    hipLaunchKernelGGL(zb_decode_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(2 * LANES), 0, st, frames, from_mid, mid_stride, d_descs, W.hdrs, W.arenas, W.astride, W.lit_cap, W.seq_cap
-#ifdef TSX_PROF2
-                       , zbprof
-#endif
-                       );
+    hipLaunchKernelGGL(zb_decode_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(2 * LANES), 0, st, frames, from_mid, mid_stride, d_descs, W.hdrs, W.arenas, W.astride, W.lit_cap, W.seq_cap, zbprof);
 }
 
 uint32_t tsx_launch_zstd_decompress_blocks(hipStream_t st, const uint8_t* frames, int from_mid, uint64_t mid_stride, tsx_chunk_desc* d_descs, uint32_t n,
                                            uint32_t max_out, uint8_t* dst, int32_t* d_status, void* bwork) {
     if (!n) return 0;
     const ZbWork W = zb_work(bwork, n, max_out, zb_arena_stride(max_out));
-    zb_launch_index_decode(st, frames, from_mid, mid_stride, d_descs, d_status, n, W, ZB_PROF_OUT);
+    zb_launch_index_decode(st, frames, from_mid, mid_stride, d_descs, d_status, n, W, g_zbprof_out);
     hipLaunchKernelGGL(zb_scatter_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(ZB_SC_WAVES * LANES), 0, st, frames, from_mid, mid_stride, d_descs, W.hdrs, W.arenas, W.astride, W.lit_cap, W.seq_cap);
     // A copy chain is at most as long as the chunk.  A pass makes two jumps IN PLACE: the first reads its source's word, the second the
     // word of what that named - either may still hold its value from before the pass (another thread has not stored yet), so what a pass
@@ -737,7 +678,7 @@ uint32_t tsx_launch_zstd_verify_blocks(hipStream_t st, const uint8_t* frames, ui
                                        uint32_t n, uint32_t max_len, const uint8_t* src_base, void* work, uint32_t* verdicts) {
     if (!n) return 0;
     const ZbWork W = zb_work(work, n, zb_verify_max(max_len), zb_verify_stride(zb_verify_max(max_len)));
-    zb_launch_index_decode(st, frames, 1, mid_stride, d_descs, d_status, n, W, nullptr);
+    zb_launch_index_decode(st, frames, 1, mid_stride, d_descs, d_status, n, W, DecLapOut{});
     hipLaunchKernelGGL(zb_verify_kernel, dim3(ZB_MAX_BLOCKS, n), dim3(ZB_SC_WAVES * LANES), 0, st, frames, mid_stride, d_descs, d_status, src_base, W.hdrs, W.arenas,
                        W.astride, W.lit_cap, W.seq_cap, verdicts);
     return 3;

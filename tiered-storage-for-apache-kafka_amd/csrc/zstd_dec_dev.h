@@ -10,9 +10,13 @@
 //     dec_seq_header      sequence count and table modes; dec_seq_table: one table from its description
 //     dec_seq_group       the sequence bit stream for one group of 64 sequences: end mark, window refill, initial states,
 //                         pass 1 (the state chain, seq_chain_step) and pass 2 (field extraction);
+//     dec_rep_offsets     pass 3: the repeat-offset history over that group, on concrete offsets (chunk-serial form) or on
+//                         references into a history not yet known (block form) - the one difference is a functor;
+//   what both forms set up the same way: dec_code_tables (LL / ML code tables into LDS), dec_huf_tree (a Huffman tree
+//   description -> the decoding table), dec_incl_scan2 (positions from lengths), DecLaps (the TSX_PROF2 lap timers);
 //   the copy helpers of the chunk-serial form's execution stage.
-// What the forms do differently stays in their own files: repeat offsets (pass 3), execution, the state the chunk-serial form
-// carries across blocks, the block form's own limits, and what a failure means to each.
+// What the forms do differently stays in their own files: execution, the state the chunk-serial form carries across blocks,
+// the block form's own limits, and what a failure means to each.
 #pragma once
 #include "zstd_common.h"
 #include "xxh64_dev.h"
@@ -99,6 +103,25 @@ struct DecLds {
     alignas(16) uint8_t hwin[4 * (ZS_HWIN + 16)];   // one window per Huffman stream
     alignas(16) uint8_t swin[ZS_DPAD + ZS_DWIN + 32];   // the sequence bit stream's window behind ZS_DPAD zero bytes (seq_chain_step reads up to 7 bytes in front of the stream)
 };
+
+// ---- lap timers of a TSX_PROF2 build (tools/prof_small.py, tools/show_prof.py, tools/zb_phase_laps.py) -------------------
+// A decoding kernel takes a DecLapOut by value and every wave keeps a DecLaps: lap(k) adds the clocks since the wave's previous
+// lap to its bucket k, put() stores bucket a (+ bucket b) in word `slot` of the 8 u64 of `row`.  Both are empty in the product
+// build: no kernel argument, no register, no instruction.
+#ifdef TSX_PROF2
+struct DecLapOut { unsigned long long* buf; };
+struct DecLaps {
+    unsigned long long t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last = (unsigned long long)clock64();
+    __device__ __forceinline__ void lap(int k) { const unsigned long long n = (unsigned long long)clock64(); t[k] += n - last; last = n; }
+    __device__ __forceinline__ void put(const DecLapOut& o, size_t row, int slot, int a, int b = -1) const { if (o.buf) o.buf[row * 8 + slot] = t[a] + (b >= 0 ? t[b] : 0); }
+};
+#else
+struct DecLapOut {};
+struct DecLaps {
+    __device__ __forceinline__ void lap(int) {}
+    __device__ __forceinline__ void put(const DecLapOut&, size_t, int, int, int = -1) const {}
+};
+#endif
 
 // ---- backward bit reader (BIT_DStream) -----------------------------------------------------------------
 struct BitR { const uint8_t* start; const uint8_t* ptr; uint64_t c; uint32_t consumed; bool bad; };
@@ -322,7 +345,9 @@ __device__ static bool fse_buildSeqTable_wave(SeqD* dt, DecLds& L, uint32_t maxS
     WAVE_SYNC();
     return true;
 }
-__device__ static uint32_t huf_readTable(DecLds& L, const uint8_t* src, uint32_t n) {
+// A Huffman tree description -> weights, canonical form (lane 0 alone: a serial parse).  Out of line on purpose: it is the one real
+// call of the decoding kernels, and inlined into them it only lengthens the live ranges of their pipelines' registers.
+__device__ __attribute__((noinline)) static uint32_t huf_readTable(DecLds& L, const uint8_t* src, uint32_t n) {
     if (n < 1) return 0;
     const uint32_t hb = src[0];
     uint32_t nw = 0, used;
@@ -396,6 +421,26 @@ __device__ static void huf_buildX_wave(DecLds& L, uint32_t lane) {
         }
         L.hufX[x] = syms | (pos << 24) | (ns << 28);
     }
+}
+// The Huffman tree description at tree / avail -> the decoding table (L.hufX, L.hufLog; L.hufValid set): lane 0 parses the
+// description, the whole wave builds the table.  One wave, every lane with the same arguments.  Returns the bytes the
+// description used, 0 (wave-uniform) when it is malformed.
+__device__ __forceinline__ static uint32_t dec_huf_tree(DecLds& L, const uint8_t* __restrict__ tree, uint32_t avail, uint32_t lane) {
+    if (lane == 0) L.scalH[0] = huf_readTable(L, tree, avail);
+    WAVE_SYNC();
+    const uint32_t used = DUNI(L.scalH[0]);
+    WAVE_SYNC();
+    if (!used) return 0;
+    huf_buildX_wave(L, lane);
+    WAVE_SYNC();
+    return used;
+}
+// The literal-length and match-length code tables (base value and extra bits of every code) and the table of the lanes that
+// run no state machine, staged in LDS by one wave for dec_seq_table and dec_seq_group; visible after the caller's barrier.
+__device__ __forceinline__ static void dec_code_tables(DecLds& L, uint32_t lane) {
+    if (lane == 0) L.zeroEntry = 0;
+    if (lane < 36) { L.cLLbase[lane] = dLLbase[lane]; L.cLLbits[lane] = dLLbits[lane]; }
+    if (lane < 53) { L.cMLbase[lane] = dMLbase[lane]; L.cMLbits[lane] = dMLbits[lane]; }
 }
 
 // ---- frame parsing, one helper per stage ----------------------------------------------------------------------------------
@@ -725,6 +770,52 @@ __device__ __forceinline__ static bool dec_seq_group(DecLds& L, DecSeqStream& S,
         ml = mbase + ((w2 >> lbits) & ((1u << mbits) - 1));
     }
     return true;
+}
+
+// Pass 3 of the sequence stage: the repeat offsets of one group (offBase, ll, valid, cnt as dec_seq_group left them), given the
+// history r0, r1, r2 the group starts from -> this lane's offset; the history is left as the next group finds it.  A sequence
+// with a new offset (code > 3) knows it already and only pushes it onto the history; the scalar loop visits just the sequences
+// that USE the history (codes 1..3), in order, first folding in the new offsets pushed since the previous visit (only the last
+// three matter).  Code c names history entry idx = c - 1 (+ 1 when the literal length is 0; idx 3 = "rep0 - 1"); idx >= 2
+// pushes the whole history down, idx 1 swaps the first two, idx 0 leaves it alone.  All on wave-uniform values, no branches.
+// What an entry IS differs between the forms - a concrete offset, or a reference into a history the block does not know yet -
+// and only "rep0 - 1" looks inside one: minus1(r0) is the caller's.
+template <class Minus1>
+__device__ __forceinline__ static uint32_t dec_rep_offsets(uint32_t offBase, uint32_t ll, bool valid, uint32_t cnt,
+                                                           uint32_t& r0, uint32_t& r1, uint32_t& r2, Minus1 minus1) {
+    uint32_t off = offBase - 3;
+    const unsigned long long ll0 = __ballot(valid && ll == 0);
+    unsigned long long users = __ballot(valid && offBase <= 3);
+    r0 = DUNI(r0); r1 = DUNI(r1); r2 = DUNI(r2);                        // the history lives in SGPRs: the loop below is scalar
+    uint32_t prev = 0;                                                  // first sequence not folded in yet
+    for (;;) {
+        const uint32_t j = users ? (uint32_t)__ffsll((long long)users) - 1 : cnt;      // next user, or the group's end
+        const uint32_t gap = j - prev;                                  // new offsets pushed by sequences [prev, j)
+        const uint32_t a1 = __builtin_amdgcn_readlane(offBase, (int)(j >= 1 ? j - 1 : 0)) - 3;
+        const uint32_t a2 = __builtin_amdgcn_readlane(offBase, (int)(j >= 2 ? j - 2 : 0)) - 3;
+        const uint32_t a3 = __builtin_amdgcn_readlane(offBase, (int)(j >= 3 ? j - 3 : 0)) - 3;
+        const uint32_t n2 = gap >= 3 ? a3 : gap == 2 ? r0 : gap == 1 ? r1 : r2;
+        const uint32_t n1 = gap >= 2 ? a2 : gap == 1 ? r0 : r1;
+        const uint32_t n0 = gap >= 1 ? a1 : r0;
+        r0 = n0; r1 = n1; r2 = n2;
+        if (!users) break;
+        users &= users - 1;
+        const uint32_t ob = __builtin_amdgcn_readlane(offBase, (int)j);
+        const uint32_t idx = ob - 1 + (uint32_t)((ll0 >> j) & 1);       // 0..3
+        const uint32_t c01 = idx == 0 ? r0 : r1, c23 = idx == 2 ? r2 : minus1(r0);
+        const uint32_t o_ = idx < 2 ? c01 : c23;
+        r2 = idx >= 2 ? r1 : r2;
+        r1 = idx >= 1 ? r0 : r1;
+        r0 = o_;
+        off = tsx_writelane(o_, j, off);
+        prev = j + 1;
+    }
+    return off;
+}
+
+// Inclusive scan of two values over the wave: positions from lengths (literal bytes and output bytes of a group's sequences).
+__device__ __forceinline__ static void dec_incl_scan2(uint32_t& a, uint32_t& t, uint32_t lane) {
+    for (int o = 1; o < LANES; o <<= 1) { const uint32_t x = __shfl_up(a, o), y = __shfl_up(t, o); if (lane >= (uint32_t)o) { a += x; t += y; } }
 }
 
 // Per-lane copy of a short, non-overlapping run (a literal run, or a match whose source is already final): up to four
