@@ -51,12 +51,30 @@ extern "C" {
  * own parsing code and compared with the chunk it was written from, before the chunk is reported: a chunk whose frame does not restore
  * it byte for byte (or whose content checksum is not the chunk's) gets status TSX_E_VERIFY and dst_len 0; the call still returns TSX_OK
  * and the other chunks are delivered.  With the flag set no chunk is reported TSX_OK unverified (TSX_E_NOMEM when the verifier finds no
- * memory).  Scope: the Zstandard frame.  The AES-GCM stage behind it is NOT re-checked - its output may already be in the caller's
- * memory, and a wrong tag is at least detected by every reader.  While verifying uploads run, the compute units reserved for fetches
+ * memory).  Scope: the Zstandard frame.  The AES-GCM stage behind it is NOT covered by this flag, nor is the copy of the frame into the
+ * caller's buffer: TSX_VERIFY_GCM below examines the bytes handed back.  While verifying uploads run, the compute units reserved for fetches
  * stay reserved (the verifier's kernels are ordinary kernels: tsx_config.fetch_quiet_ms).  On a verifying transform tsx_timing's
  * unzstd_ms / unzstd_launches are the verifier's.  Without TSX_COMPRESS it is TSX_E_INVAL; detransform accepts and ignores it
  * (callers build one flags word for both directions).  (0x10 stays unassigned.) */
 #define TSX_VERIFY 0x20u
+/* Modifier of TSX_ENCRYPT on transform: verify on upload, AES-GCM stage.  Every chunk that is TSX_OK behind the GCM stage is examined
+ * on the device, in the bytes the device DELIVERED - IV || C || TAG where it wrote them: the caller's device buffer, the context's
+ * output buffer (copy path), or the caller's registered host buffer (zero-copy output, read back over PCIe) - before it is reported:
+ *   dst_len is the plaintext length + 28; the 12 delivered IV bytes are descs[i].iv; AES-256-CTR of the delivered ciphertext under the
+ *   batch key and that IV is, byte for byte, the plaintext the stage was given (the chunk's Zstandard frame in the staging buffer when
+ *   compressing, the chunk's source bytes on the device otherwise); GHASH over the AAD, the delivered ciphertext and the length block,
+ *   xor E_K(J0), is the delivered tag.
+ * A chunk that fails gets status TSX_E_VERIFY and dst_len 0; the call still returns TSX_OK and the other chunks are delivered (TSX_VERIFY's
+ * semantics).  With the flag set no chunk is reported TSX_OK unexamined (TSX_E_NOMEM when the verifier finds no memory for its verdicts).
+ * With TSX_VERIFY as well the Zstandard verifier runs first and the chunks it failed are skipped; the chain is then
+ * source == decode(frame), frame == decrypt(delivered), tag valid.  Valid with or without TSX_COMPRESS (encrypt-only uploads), TSX_CRC,
+ * TSX_ZSTD_CHECKSUM and TSX_VERIFY; without TSX_ENCRYPT it is TSX_E_INVAL; detransform accepts and ignores it.  The verifier's kernels are
+ * ordinary kernels (next to the compressor service the batch counts as a fetch having been seen: the reserved compute units stay
+ * reserved) and add to tsx_timing's gcm_ms / gcm_launches.
+ * NOT covered: the copy engine's device-to-host copy on the copy path (a destination the device cannot address); the host's memmove of a
+ * packed batch that is packed down in place; a common-mode error of the AES and GHASH device functions, which the encrypting and the
+ * verifying kernels share (the test suite's comparison with OpenSSL guards those).  (0x10 and 0x40 stay unassigned.) */
+#define TSX_VERIFY_GCM 0x80u
 
 /* where src/dst live */
 /* host pointers.  The batch is cut into pieces whose H2D copy, kernels and D2H copy overlap: pieces of >= 64 MiB in order on three
@@ -94,7 +112,7 @@ extern "C" {
                                    "Invalid decompressed size: n" (DecompressionChunkEnumeration.java:42-44) */
 #define TSX_E_SHORT_CHUNK   -8  /* encrypted chunk shorter than IV+TAG                            */
 #define TSX_E_UNSUPPORTED   -9
-#define TSX_E_VERIFY        -10 /* TSX_VERIFY: the frame written for this chunk does not restore it (per chunk)  */
+#define TSX_E_VERIFY        -10 /* TSX_VERIFY / TSX_VERIFY_GCM: the frame written for this chunk does not restore it (per chunk)  */
 
 /* Per-chunk descriptor; mirrors io.aiven.kafka.tieredstorage.Chunk (core/.../Chunk.java:21-36:
  * id, originalPosition, originalSize, transformedPosition, transformedSize) with the in/out split
@@ -116,7 +134,7 @@ typedef struct tsx_chunk_desc {
 /* Per-batch parameters: one (data key, AAD) pair per segment
  * (AesEncryptionProvider.createDataKeyAndAAD, core/.../security/AesEncryptionProvider.java:52-58). */
 typedef struct tsx_batch_params {
-    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC [| TSX_ZSTD_CHECKSUM] [| TSX_VERIFY]     */
+    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC [| TSX_ZSTD_CHECKSUM] [| TSX_VERIFY] [| TSX_VERIFY_GCM] */
     uint32_t aad_len;      /* reference: 32                                                         */
     uint8_t  key[32];      /* AES-256 data key (SecretKey.getEncoded())                             */
     uint8_t  aad[64];

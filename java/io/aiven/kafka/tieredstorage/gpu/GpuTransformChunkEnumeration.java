@@ -38,6 +38,7 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
     private final int zstdLevel;             // 0: the library default (3)
     private final boolean zstdChecksum;      // content checksum in every frame
     private final boolean zstdVerify;        // every frame is read back on the device and compared with its chunk
+    private final boolean gcmVerify;         // every delivered IV || C || TAG is decrypted and authenticated on the device
     private final int device;
     private final Integer transformedChunkSize;
     private final ArrayDeque<byte[]> ready = new ArrayDeque<>();
@@ -121,6 +122,22 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
                                         final SecureRandom random, final int zstdProfile, final int segmentHash,
                                         final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
                                         final boolean zstdVerify) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, readAhead, zstdLevel,
+            zstdChecksum, zstdVerify, false);
+    }
+
+    /**
+     * @param gcmVerify verify on upload, AES-GCM stage, plugin configuration key {@code encryption.verify} (INTEGRATION.md 2), default
+     *                  false: the IV || C || TAG the device has delivered for a chunk - in this thread's pinned output buffer - is read
+     *                  back, decrypted and authenticated on the device against the bytes that went into the stage, before the chunk is
+     *                  handed on.  A chunk that fails raises what any failed chunk raises ({@link TsxNative#E_VERIFY}): the segment copy
+     *                  fails, the broker retries it and keeps the local segment.  Refused when the chain does not encrypt.
+     */
+    public GpuTransformChunkEnumeration(final TransformChunkEnumeration inner, final boolean compress,
+                                        final DataKeyAndAAD keyAndAad, final int batchChunks,
+                                        final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                        final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
+                                        final boolean zstdVerify, final boolean gcmVerify) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
         if (zstdChecksum && !compress) {
             throw new IllegalArgumentException("Zstd checksum needs compression");
@@ -130,6 +147,10 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
             throw new IllegalArgumentException("Zstd verification needs compression");
         }
         this.zstdVerify = zstdVerify;
+        if (gcmVerify && keyAndAad == null) {
+            throw new IllegalArgumentException("GCM verification needs encryption");
+        }
+        this.gcmVerify = gcmVerify;
         if (zstdLevel < 0 || zstdLevel > 3) {
             throw new IllegalArgumentException("Zstd level must be 1, 2 or 3 (0: library default), " + zstdLevel + " given");
         }
@@ -229,7 +250,8 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
         }
         final int flags = (compress ? TsxNative.COMPRESS : 0) | (keyAndAad != null ? TsxNative.ENCRYPT : 0)
             | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0)
-            | (zstdVerify ? TsxNative.VERIFY : 0);
+            | (zstdVerify ? TsxNative.VERIFY : 0)
+            | (gcmVerify ? TsxNative.VERIFY_GCM : 0);
         // per-thread, reused, pinned (registered with the device): the compressor waves write every chunk's IV || C || TAG straight into the
         // dst buffer's slots (zero-copy output, DESIGN.md section 1) - a pageable buffer would send the batch through copy engines instead.
         // Footprint per thread: ~2.1 GiB at 256 x 4 MiB (source batch + bound-sized output slots), INTEGRATION.md section 4.

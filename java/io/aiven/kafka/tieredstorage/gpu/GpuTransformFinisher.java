@@ -123,6 +123,7 @@ public class GpuTransformFinisher {
     private final int zstdLevel;             // 0: the library default (3)
     private final boolean zstdChecksum;      // content checksum in every frame
     private final boolean zstdVerify;        // every frame is read back on the device and compared with its chunk
+    private final boolean gcmVerify;         // every delivered IV || C || TAG is decrypted and authenticated on the device
     private final int device;
     private final boolean readAhead;
     private final Bucket rateLimitingBucket;
@@ -189,6 +190,22 @@ public class GpuTransformFinisher {
                                 final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
                                 final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
                                 final boolean zstdVerify) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, originalFileSize,
+            chunkingEnabled, rateLimitingBucket, readAhead, zstdLevel, zstdChecksum, zstdVerify, false);
+    }
+
+    /**
+     * @param gcmVerify verify on upload, AES-GCM stage, plugin configuration key {@code encryption.verify} (INTEGRATION.md 2), default
+     *                  false: the IV || C || TAG the device has delivered for a chunk - in this thread's pinned output buffer - is read
+     *                  back, decrypted and authenticated on the device against the bytes that went into the stage, before the chunk is
+     *                  handed on.  A chunk that fails raises what any failed chunk raises ({@link TsxNative#E_VERIFY}): the segment copy
+     *                  fails, the broker retries it and keeps the local segment.  Refused when the chain does not encrypt.
+     */
+    public GpuTransformFinisher(final TransformChunkEnumeration inner, final boolean compress, final DataKeyAndAAD keyAndAad,
+                                final int batchChunks, final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
+                                final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
+                                final boolean zstdVerify, final boolean gcmVerify) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
         if (zstdChecksum && !compress) {
             throw new IllegalArgumentException("Zstd checksum needs compression");
@@ -198,6 +215,10 @@ public class GpuTransformFinisher {
             throw new IllegalArgumentException("Zstd verification needs compression");
         }
         this.zstdVerify = zstdVerify;
+        if (gcmVerify && keyAndAad == null) {
+            throw new IllegalArgumentException("GCM verification needs encryption");
+        }
+        this.gcmVerify = gcmVerify;
         if (zstdLevel < 0 || zstdLevel > 3) {
             throw new IllegalArgumentException("Zstd level must be 1, 2 or 3 (0: library default), " + zstdLevel + " given");
         }
@@ -241,7 +262,8 @@ public class GpuTransformFinisher {
     private int flags() {
         return (compress ? TsxNative.COMPRESS : 0) | (keyAndAad != null ? TsxNative.ENCRYPT : 0)
             | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0)
-            | (zstdVerify ? TsxNative.VERIFY : 0);
+            | (zstdVerify ? TsxNative.VERIFY : 0)
+            | (gcmVerify ? TsxNative.VERIFY_GCM : 0);
     }
 
     private static long align16(final long v) {

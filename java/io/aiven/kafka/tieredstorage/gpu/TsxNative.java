@@ -22,12 +22,19 @@ public final class TsxNative {
      * {@link #E_VERIFY}.  Detransform accepts and ignores the flag.
      */
     public static final int VERIFY = 0x20;
+    /**
+     * With {@link #ENCRYPT} on transform: verify on upload, AES-GCM stage ({@code encryption.verify}).  The IV || C || TAG the device has
+     * delivered for a chunk is decrypted and authenticated on the device, against the bytes the stage was given, before the chunk is
+     * reported; a chunk that fails has status {@link #E_VERIFY}.  Without {@link #ENCRYPT} the batch is refused; detransform accepts and
+     * ignores the flag.
+     */
+    public static final int VERIFY_GCM = 0x80;
 
     public static final int OK = 0;
     public static final int E_TAG_MISMATCH = -5;
     public static final int E_BAD_FRAME = -6;
     public static final int E_BAD_SIZE = -7;
-    /** Under {@link #VERIFY}: the frame written for this chunk does not restore it (per chunk; the batch call itself succeeds). */
+    /** Under {@link #VERIFY} / {@link #VERIFY_GCM}: what was written for this chunk does not restore it (per chunk; the batch call itself succeeds). */
     public static final int E_VERIFY = -10;
 
     /** Size of one tsx_chunk_desc (include/tsxform.h), written/read through a direct little-endian ByteBuffer. */

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libtsxform.so")
 COMPRESS, ENCRYPT, CRC = 1, 2, 4
 ZSTD_CHECKSUM = 8        # with COMPRESS on transform: frames carry a content checksum (TSX_ZSTD_CHECKSUM); every fetch verifies one that is there
 VERIFY = 0x20            # with COMPRESS on transform: every frame is read back and compared with its chunk before it is reported (TSX_VERIFY)
+VERIFY_GCM = 0x80        # with ENCRYPT on transform: the delivered IV||C||TAG of every chunk is decrypted and authenticated on the device before it is reported (TSX_VERIFY_GCM)
 MEM_HOST, MEM_DEVICE, MEM_HOST_PACKED = 0, 1, 2
 OK, E_INVAL, E_DEVICE, E_NOMEM, E_DST_TOO_SMALL, E_TAG_MISMATCH, E_BAD_FRAME, E_BAD_SIZE, E_SHORT_CHUNK, E_UNSUPPORTED = \
     0, -1, -2, -3, -4, -5, -6, -7, -8, -9
@@ -149,7 +150,7 @@ class Native:
     def debug_config(self, key, value):
         """Test / measurement hook: set one configuration field of the loaded library, return the previous value."""
         old = self.lib.tsx_debug_config(key.encode(), int(value))
-        if old == E_INVAL and key not in ("pool_idle_bytes", "verify_damage_src_chunk", "verify_damage_frame_chunk"):     # (fields whose "none" is -1)
+        if old == E_INVAL and key not in ("pool_idle_bytes", "verify_damage_src_chunk", "verify_damage_frame_chunk", "verify_damage_out_chunk"):     # (fields whose "none" is -1)
             raise KeyError(key)
         return old
 

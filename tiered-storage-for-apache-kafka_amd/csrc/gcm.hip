@@ -413,6 +413,186 @@ __global__ __launch_bounds__(64) void gcm_final_kernel(const tsx_aes_tables* __r
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// verify on upload, GCM stage (TSX_VERIFY_GCM): the delivered IV || C || TAG of every chunk against the plaintext it was made from
+// (the verdict word's bits: tsx_internal.h)
+// ---------------------------------------------------------------------------------------------------
+// The GHASH of one chunk out of its sub-blocks' partial values, by one wave (every lane gets the result): gcm_final_kernel's lane-parallel
+// loop over the sub-blocks, the AAD term and the length term, restated for the verifier (that kernel keeps its own text).
+__device__ static inline tsx_gf128 gcm_stitch_wave(const tsx_gcm_key* __restrict__ key, const uint32_t* __restrict__ chunk_partials, uint32_t n, uint32_t lane) {
+    const uint32_t nb = (n + 15) >> 4;
+    const uint32_t nsub = (nb + (uint32_t)TSX_GCM_SUB_BLOCKS - 1) / (uint32_t)TSX_GCM_SUB_BLOCKS;
+    // AAD blocks: Horner with H (every lane computes the same value: as long as one lane doing it), scaled below past the ciphertext and the length block
+    const uint32_t alen = key->aad_len;
+    tsx_gf128 a; a.hi = 0; a.lo = 0;
+    for (uint32_t o = 0; o < alen; o += 16) {
+        tsx_gf128 x = gf_from_bytes(key->aad + o, min(16u, alen - o));
+        a.hi ^= x.hi; a.lo ^= x.lo;
+        a = gf_mul(a, key->h);
+    }
+    tsx_gf128 acc; acc.hi = 0; acc.lo = 0;
+    for (uint32_t it = lane; it < nsub + 2; it += 64) {
+        tsx_gf128 z; uint32_t e;
+        if (it < nsub) {
+            const uint32_t* pp = chunk_partials + (size_t)it * 4;
+            z.hi = ((uint64_t)pp[1] << 32) | pp[0]; z.lo = ((uint64_t)pp[3] << 32) | pp[2];
+            const uint32_t jend = min((it + 1) * (uint32_t)TSX_GCM_SUB_BLOCKS, nb);
+            e = nb - jend + 2;                                          // block j carries H^(nb-j+1): length block follows
+        } else if (it == nsub) {
+            z = a; e = nb + 1;                                          // (zero without AAD)
+        } else {
+            z.hi = (uint64_t)alen * 8; z.lo = (uint64_t)n * 8; e = 1;   // length block [len(A)]64 || [len(C)]64 in bits, times H
+        }
+        const tsx_gf128 r = gf_mul(z, gf_pow_h_tab(key, e));
+        acc.hi ^= r.hi; acc.lo ^= r.lo;
+    }
+    for (int o = 32; o; o >>= 1) { acc.hi ^= __shfl_xor(acc.hi, o); acc.lo ^= __shfl_xor(acc.lo, o); }
+    return acc;
+}
+
+// One step of a lane's strided GHASH, as gcm_ctr_ghash_kernel's loop has it (that kernel keeps its own text: its register allocation is
+// measured): Y <- Y * H^256 xor X, X the ciphertext block as four little-endian words (`hs`: the 4-bit Shoup
+// tables of H^256 in LDS, one conflict-free 16-byte read per nibble).
+__device__ static inline void ghash_step_h256(const tsx_gf128* hs, tsx_gf128& y, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3) {
+    tsx_gf128 z; z.hi = 0; z.lo = 0;
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        tsx_gf128 e0 = hs[q * 16 + ((y.hi >> (60 - 4 * q)) & 15u)];
+        tsx_gf128 e1 = hs[(16 + q) * 16 + ((y.lo >> (60 - 4 * q)) & 15u)];
+        z.hi ^= e0.hi ^ e1.hi; z.lo ^= e0.lo ^ e1.lo;
+    }
+    tsx_gf128 x = gf_from_le_words(x0, x1, x2, x3);
+    y.hi = z.hi ^ x.hi; y.lo = z.lo ^ x.lo;
+}
+
+// The encrypt kernel's shape (one 64 KiB sub-block per workgroup, thread t owns blocks t, t + 256, ...: a wave's loads are contiguous 16 B
+// per lane, so delivered bytes in host memory cross PCIe once, coalesced), run the other way round: the delivered ciphertext block is
+// loaded ONCE, XORed with the keystream of counter IV || 2 + j and compared with the reference block; the same registers feed the strided
+// GHASH.  chunks[i]: in_off = the reference plaintext in `ref`, out_off = the delivered IV || C || TAG in `delivered`, len = the plaintext
+// length.  The counter's IV is the descriptor's: the finaliser fails a chunk whose delivered IV is another, so for every chunk that
+// passes it WAS the delivered one - and the 12 bytes are not fetched by every workgroup.  Stores: the GHASH partial and one mismatch word.
+__global__ __launch_bounds__(TSX_GCM_THREADS) void gcm_verify_kernel(
+        const tsx_aes_tables* __restrict__ aes, const tsx_gcm_key* __restrict__ key, const tsx_gcm_chunk* __restrict__ chunks,
+        uint32_t max_sub, const uint8_t* __restrict__ ref, const uint8_t* __restrict__ delivered, uint32_t* __restrict__ partials,
+        uint32_t* __restrict__ mismatch) {
+    __shared__ uint32_t lds_t0[256 * 32];          // T0 replicated per bank: entry x, copy b at [x*32 + b]
+    __shared__ tsx_gf128 lds_hs[32 * 16];          // Shoup tables of H^256; the fold reuses entries 0..7 (gcm_ctr_ghash_kernel: 32 granules, 4 workgroups per CU)
+    static_assert(sizeof(lds_t0) + sizeof(lds_hs) == 32 * 1280, "LDS granules");
+    const uint32_t t = threadIdx.x;
+    const uint32_t ci = blockIdx.x / max_sub, sub = blockIdx.x % max_sub;
+    const tsx_gcm_chunk ch = chunks[ci];
+    const uint32_t n = ch.len;
+    const uint32_t nb = (n + 15) >> 4;
+    const uint32_t j0 = sub * TSX_GCM_SUB_BLOCKS;
+    uint32_t* my_partial = partials + ((size_t)ci * max_sub + sub) * 4;
+    if (ch.skip || j0 >= nb) {                                          // uniform exit
+        if (t < 4) my_partial[t] = 0;
+        if (t == 4) mismatch[(size_t)ci * max_sub + sub] = 0;
+        return;
+    }
+    const uint32_t j1 = min(j0 + (uint32_t)TSX_GCM_SUB_BLOCKS, nb);
+    for (uint32_t i = t; i < 256 * 32; i += TSX_GCM_THREADS) lds_t0[i] = aes->te0[i >> 5];
+    for (uint32_t i = t; i < 512; i += TSX_GCM_THREADS) lds_hs[i] = (&key->hstride_tab[0][0])[i];
+    __syncthreads();
+    const uint32_t bank = t & 31;
+    auto T0 = [&](uint32_t x) { return lds_t0[(x << 5) | bank]; };
+    const uint8_t* pt = ref + ch.in_off;
+    const uint8_t* ct = delivered + ch.out_off + 12;
+    const uint8_t* ivp = ch.iv;
+    const uint32_t iv0 = (uint32_t)ivp[0] | ((uint32_t)ivp[1] << 8) | ((uint32_t)ivp[2] << 16) | ((uint32_t)ivp[3] << 24);
+    const uint32_t iv1 = (uint32_t)ivp[4] | ((uint32_t)ivp[5] << 8) | ((uint32_t)ivp[6] << 16) | ((uint32_t)ivp[7] << 24);
+    const uint32_t iv2 = (uint32_t)ivp[8] | ((uint32_t)ivp[9] << 8) | ((uint32_t)ivp[10] << 16) | ((uint32_t)ivp[11] << 24);
+    tsx_gf128 y; y.hi = 0; y.lo = 0;
+    uint32_t last = 0, diff = 0;
+    bool any = false;
+    for (uint32_t j = j0 + t; j < j1; j += TSX_GCM_THREADS) {
+        uint32_t k0 = iv0, k1 = iv1, k2 = iv2, k3 = bswap32(2u + j);
+        aes256_encrypt(key->rk, T0, k0, k1, k2, k3);
+        const uint32_t m = min(16u, n - (j << 4));
+        uint32_t c0, c1, c2, c3, p0, p1, p2, p3;
+        if (m == 16) {
+            const tsx_u128a4 v = *reinterpret_cast<const tsx_u128a4*>(ct + ((size_t)j << 4));
+            const tsx_u128a4 w = *reinterpret_cast<const tsx_u128a4*>(pt + ((size_t)j << 4));
+            c0 = v.v[0]; c1 = v.v[1]; c2 = v.v[2]; c3 = v.v[3];
+            p0 = w.v[0]; p1 = w.v[1]; p2 = w.v[2]; p3 = w.v[3];
+        } else {                                                        // the last block: bytewise, zero padded (for GHASH and for the compare alike)
+            uint64_t cl = 0, chh = 0, pl = 0, ph = 0;
+            for (uint32_t b = 0; b < m; b++) {
+                const uint64_t cb = ct[((size_t)j << 4) + b], pb = pt[((size_t)j << 4) + b];
+                if (b < 8) { cl |= cb << (8 * b); pl |= pb << (8 * b); } else { chh |= cb << (8 * (b - 8)); ph |= pb << (8 * (b - 8)); }
+            }
+            // the keystream behind the message's end takes no part (1 <= m <= 15)
+            const uint64_t ml = m >= 8 ? ~0ull : (1ull << (8 * m)) - 1, mh = m <= 8 ? 0ull : (1ull << (8 * (m - 8))) - 1;
+            k0 &= (uint32_t)ml; k1 &= (uint32_t)(ml >> 32); k2 &= (uint32_t)mh; k3 &= (uint32_t)(mh >> 32);
+            c0 = (uint32_t)cl; c1 = (uint32_t)(cl >> 32); c2 = (uint32_t)chh; c3 = (uint32_t)(chh >> 32);
+            p0 = (uint32_t)pl; p1 = (uint32_t)(pl >> 32); p2 = (uint32_t)ph; p3 = (uint32_t)(ph >> 32);
+        }
+        diff |= (c0 ^ k0 ^ p0) | (c1 ^ k1 ^ p1) | (c2 ^ k2 ^ p2) | (c3 ^ k3 ^ p3);
+        ghash_step_h256(lds_hs, y, c0, c1, c2, c3);
+        last = j; any = true;
+    }
+    tsx_gf128 r; r.hi = 0; r.lo = 0;
+    if (any) r = gf_mul(y, key->hpow[j1 - 1 - last]);
+    for (int o = 32; o; o >>= 1) { r.hi ^= __shfl_xor(r.hi, o); r.lo ^= __shfl_xor(r.lo, o); }
+    const bool wave_diff = __ballot(diff != 0) != 0;
+    __syncthreads();                                                    // every lane has made its last lookup in lds_hs (gf_mul reads no table)
+    if ((t & 63) == 0) { lds_hs[t >> 6] = r; lds_hs[4 + (t >> 6)].hi = wave_diff ? 1u : 0u; }
+    __syncthreads();
+    if (t == 0) {
+        tsx_gf128 s; s.hi = 0; s.lo = 0;
+        uint64_t bad = 0;
+        for (int w = 0; w < TSX_GCM_THREADS / 64; w++) { s.hi ^= lds_hs[w].hi; s.lo ^= lds_hs[w].lo; bad |= lds_hs[4 + w].hi; }
+        my_partial[0] = (uint32_t)s.hi; my_partial[1] = (uint32_t)(s.hi >> 32);
+        my_partial[2] = (uint32_t)s.lo; my_partial[3] = (uint32_t)(s.lo >> 32);
+        mismatch[(size_t)ci * max_sub + sub] = bad ? 1u : 0u;
+    }
+}
+
+// One wave per chunk: the tag out of the sub-blocks' partial values (gcm_stitch_wave) and E_K(J0) of the DELIVERED IV against the
+// delivered tag, the delivered IV against the descriptor's, the sub-blocks' mismatch words, dst_len against the plaintext length: one
+// verdict word per chunk (verdict != nullptr) and / or TSX_E_VERIFY in status[] (status != nullptr) for a chunk that fails.
+// chunks[i].skip: 1 = the chunk had failed before (not examined, verdict 0), 2 = its dst_len is not len + 28 (fails unread).
+__global__ __launch_bounds__(64) void gcm_verify_final_kernel(const tsx_aes_tables* __restrict__ aes, const tsx_gcm_key* __restrict__ key,
+                                                              const tsx_gcm_chunk* __restrict__ chunks, const tsx_chunk_desc* __restrict__ descs,
+                                                              uint32_t max_sub, const uint8_t* __restrict__ delivered, const uint32_t* __restrict__ partials,
+                                                              const uint32_t* __restrict__ mismatch, uint32_t* __restrict__ verdict, int32_t* __restrict__ status) {
+    const uint32_t ci = blockIdx.x, lane = threadIdx.x;
+    const tsx_gcm_chunk ch = chunks[ci];
+    if (ch.skip == 1) { if (lane == 0 && verdict) verdict[ci] = 0; return; }
+    uint32_t v = TSX_GV_SEEN;
+    const uint32_t n = ch.len;
+    if (ch.skip || descs[ci].dst_len != n + 28) v |= TSX_GV_LEN;       // (uniform: nothing of such a chunk is read)
+    else {
+        const tsx_gf128 acc = gcm_stitch_wave(key, partials + (size_t)ci * max_sub * 4, n, lane);
+        const uint32_t nsub = (((n + 15) >> 4) + (uint32_t)TSX_GCM_SUB_BLOCKS - 1) / (uint32_t)TSX_GCM_SUB_BLOCKS;
+        uint32_t bad = 0;
+        for (uint32_t it = lane; it < nsub; it += 64) bad |= mismatch[(size_t)ci * max_sub + it];
+        if (__ballot(bad != 0) != 0) v |= TSX_GV_PLAIN;
+        if (lane == 0) {
+            const uint8_t* ivp = delivered + ch.out_off;
+            uint32_t ivdiff = 0;
+            for (int i = 0; i < 12; i++) ivdiff |= (uint32_t)(ivp[i] ^ descs[ci].iv[i]);
+            if (ivdiff) v |= TSX_GV_IV;
+            uint32_t k0 = (uint32_t)ivp[0] | ((uint32_t)ivp[1] << 8) | ((uint32_t)ivp[2] << 16) | ((uint32_t)ivp[3] << 24);
+            uint32_t k1 = (uint32_t)ivp[4] | ((uint32_t)ivp[5] << 8) | ((uint32_t)ivp[6] << 16) | ((uint32_t)ivp[7] << 24);
+            uint32_t k2 = (uint32_t)ivp[8] | ((uint32_t)ivp[9] << 8) | ((uint32_t)ivp[10] << 16) | ((uint32_t)ivp[11] << 24);
+            uint32_t k3 = 0x01000000u;                                  // J0 = IV || 0^31 || 1
+            auto T0 = [&](uint32_t x) { return aes->te0[x]; };
+            aes256_encrypt(key->rk, T0, k0, k1, k2, k3);
+            uint32_t tagw[4];
+            gf_to_le_words(acc, tagw);
+            tagw[0] ^= k0; tagw[1] ^= k1; tagw[2] ^= k2; tagw[3] ^= k3;
+            const uint8_t* tg = delivered + ch.out_off + 12 + n;
+            uint32_t tdiff = 0;
+            for (int i = 0; i < 16; i++) tdiff |= (uint32_t)(tg[i] ^ (uint8_t)(tagw[i >> 2] >> (8 * (i & 3))));
+            if (tdiff) v |= TSX_GV_TAG;
+        }
+    }
+    if (lane != 0) return;
+    if (verdict) verdict[ci] = v;
+    if (status && v != TSX_GV_SEEN) status[ci] = TSX_E_VERIFY;
+}
+
 void tsx_launch_gcm_setup(hipStream_t st, const tsx_aes_tables* d_aes, const uint8_t* d_key32, const uint8_t* d_aad,
                           uint32_t aad_len, tsx_gcm_key* d_key) {
     hipLaunchKernelGGL(gcm_setup_kernel, dim3(1), dim3(256), 0, st, d_aes, d_key32, d_aad, aad_len, d_key);
@@ -428,4 +608,17 @@ void tsx_launch_gcm(hipStream_t st, const tsx_aes_tables* d_aes, const tsx_gcm_k
                        in, out, d_partials, decrypt);
     hipLaunchKernelGGL(gcm_final_kernel, dim3(n), dim3(64), 0, st, d_aes, d_key, d_chunks, max_sub, in, out,
                        (const uint32_t*)d_partials, d_status, decrypt);
+}
+
+void tsx_launch_gcm_verify(hipStream_t st, const tsx_aes_tables* d_aes, const tsx_gcm_key* d_key, const tsx_gcm_chunk* d_chunks,
+                           const tsx_chunk_desc* descs, uint32_t n, uint32_t max_len, const uint8_t* ref, const uint8_t* delivered,
+                           uint32_t* d_partials, uint32_t* verdicts, int32_t* d_status) {
+    if (!n) return;
+    uint32_t max_sub = (max_len + TSX_GCM_SUB_BYTES - 1) / TSX_GCM_SUB_BYTES;
+    if (max_sub == 0) max_sub = 1;
+    uint32_t* const mismatch = d_partials + (size_t)n * max_sub * 4;
+    hipLaunchKernelGGL(gcm_verify_kernel, dim3(n * max_sub), dim3(TSX_GCM_THREADS), 0, st, d_aes, d_key, d_chunks, max_sub, ref, delivered,
+                       d_partials, mismatch);
+    hipLaunchKernelGGL(gcm_verify_final_kernel, dim3(n), dim3(64), 0, st, d_aes, d_key, d_chunks, descs, max_sub, delivered,
+                       (const uint32_t*)d_partials, (const uint32_t*)mismatch, verdicts, d_status);
 }

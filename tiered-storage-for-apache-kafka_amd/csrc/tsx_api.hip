@@ -43,7 +43,8 @@ extern "C" long long tsx_debug_config(const char* key, long long value) {
     CFG_FIELD(stages_separate, bool) CFG_FIELD(no_pipeline, bool) CFG_FIELD(no_zero_copy_out, bool) CFG_FIELD(zero_copy_packed, bool)
     CFG_FIELD(gcm_setup_kernel, bool) CFG_FIELD(no_dec_pieces, bool) CFG_FIELD(debug, bool) CFG_FIELD(svc_normal_priority, bool) CFG_FIELD(svc_keep_waves, uint32_t) CFG_FIELD(fetch_quiet_ms, uint32_t) CFG_FIELD(trace, bool)
     CFG_FIELD(verify_damage_src_chunk, long long) CFG_FIELD(verify_damage_src_off, long long) CFG_FIELD(verify_damage_frame_chunk, long long)
-    CFG_FIELD(verify_damage_frame_off, long long) CFG_FIELD(verify_slice_chunks, uint32_t) CFG_FIELD(verify_force_fallback, bool)
+    CFG_FIELD(verify_damage_frame_off, long long) CFG_FIELD(verify_damage_out_chunk, long long) CFG_FIELD(verify_damage_out_off, long long)
+    CFG_FIELD(verify_slice_chunks, uint32_t) CFG_FIELD(verify_force_fallback, bool)
 #undef CFG_FIELD
     return TSX_E_INVAL;
 }
@@ -260,7 +261,8 @@ static int ctx_reserve(tsx_ctx* c, uint32_t n, uint32_t max_len, uint32_t max_ou
     size_t bound = tsx_transformed_bound(max_len, flags & TSX_COMPRESS) + 64;
     size_t subs = (bound + TSX_GCM_SUB_BYTES - 1) / TSX_GCM_SUB_BYTES + 1;
     size_t crc_subs = ((size_t)(max_out > max_len ? max_out : max_len) + TSX_CRC_SUB_BYTES - 1) / TSX_CRC_SUB_BYTES + 1;
-    size_t per_chunk = subs * 4 > crc_subs ? subs * 4 : crc_subs;
+    const size_t gcm_words = (flags & TSX_VERIFY_GCM) ? 5 : 4;        // (the GCM verifier keeps a mismatch word per sub-block behind the partial values)
+    size_t per_chunk = subs * gcm_words > crc_subs ? subs * gcm_words : crc_subs;
     int rc = grow(c->dev, &c->d_partials, &c->partials_cap, (size_t)n * per_chunk);
     if (rc) return rc;
     c->partials_per_chunk = per_chunk;

@@ -380,6 +380,20 @@ void verifier_destroy(tsx_device& d) {
     if (d.verifier) { (void)hipFree(d.verifier->work); (void)hipFree(d.verifier->full); delete d.verifier; d.verifier = nullptr; }
 }
 
+// The context's verdict words, pinned: room for `chunks` chunks of ZB_VERDICT_WORDS words each.  *ok = false: the host has no memory for them.
+static int verdicts_reserve(tsx_ctx* c, size_t chunks, bool* ok) {
+    *ok = false;
+    if (c->verdicts_cap < chunks) {
+        svc_free_host(c->dev, c->h_verdicts); c->h_verdicts = nullptr; c->hd_verdicts = nullptr; c->verdicts_cap = 0;
+        const size_t cap = chunks + chunks / 4 + 16;
+        if (hipHostMalloc((void**)&c->h_verdicts, cap * ZB_VERDICT_WORDS * 4, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); c->h_verdicts = nullptr; return TSX_OK; }
+        HIPCHK(hipHostGetDevicePointer((void**)&c->hd_verdicts, c->h_verdicts, 0));
+        c->verdicts_cap = cap;
+    }
+    *ok = true;
+    return TSX_OK;
+}
+
 // Chunks [sb.lo, sb.lo + sb.n) - a member that has just completed - before anything of them is reported: vcode[i] = 0 (the frame restores
 // the chunk, or the chunk was not TSX_OK anyway), TSX_E_VERIFY, or TSX_E_NOMEM (never "not looked at").  The kernels are ordinary kernels
 // on a chip that compressor waves fill: the piece claims the reserved CUs like a fetch and waits with the fetch side's safety net.
@@ -388,6 +402,7 @@ static int verify_piece(tsx_run& r, const tsx_sub& sb, bool self_status, int32_t
     tsx_device* dev = c->dev;
     tsx_timing& t = c->timing;
     for (uint32_t i = 0; i < sb.n; i++) vcode[sb.lo + i] = TSX_E_NOMEM;
+    int rc_ = TSX_OK;
     tsx_verifier* const V = verifier_of(dev);
     if (!V) return TSX_OK;
     uint32_t max_len = 0;
@@ -396,13 +411,8 @@ static int verify_piece(tsx_run& r, const tsx_sub& sb, bool self_status, int32_t
     uint32_t slice = g_cfg.verify_slice_chunks ? g_cfg.verify_slice_chunks : (uint32_t)std::min<size_t>(TSX_VERIFY_SLICE_BYTES / per_chunk, sb.n);
     if (slice < 1) slice = 1;
     if (slice > sb.n) slice = sb.n;
-    if (c->verdicts_cap < slice) {
-        svc_free_host(dev, c->h_verdicts); c->h_verdicts = nullptr; c->hd_verdicts = nullptr; c->verdicts_cap = 0;
-        const size_t cap = (size_t)slice + slice / 4 + 16;
-        if (hipHostMalloc((void**)&c->h_verdicts, cap * ZB_VERDICT_WORDS * 4, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); c->h_verdicts = nullptr; return TSX_OK; }
-        HIPCHK(hipHostGetDevicePointer((void**)&c->hd_verdicts, c->h_verdicts, 0));
-        c->verdicts_cap = cap;
-    }
+    bool have_verdicts = false;
+    if ((rc_ = verdicts_reserve(c, slice, &have_verdicts)) || !have_verdicts) return rc_;
     svc_foreground_scope fg(dev);
     std::lock_guard<std::mutex> lk(V->mu);
     const size_t head = ((size_t)slice * (2 * sizeof(tsx_chunk_desc) + 8) + 255) & ~(size_t)255;
@@ -457,6 +467,74 @@ static int verify_piece(tsx_run& r, const tsx_sub& sb, bool self_status, int32_t
             vcode[j] = W[ZB_V_FAIL] || !W[ZB_V_SEEN] ? TSX_E_VERIFY : TSX_OK;
         }
         if (src_hit) { hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, c->st, src_hit); HIPCHK(hipStreamSynchronize(c->st)); }
+    }
+    HIPCHK(hipGetLastError());
+    return TSX_OK;
+}
+
+// ---- verify on upload, GCM stage (TSX_VERIFY_GCM) of a compressing batch ---------------------------------------------------------------
+// The verifier's work items for chunks 0 .. n - 1 of a piece, from the piece's descriptors in pinned memory as the host has left them
+// (status, dst_off, dst_len, iv: the waves', or separate_finish's, with the Zstandard verifier's verdicts applied) and the frame sizes:
+// reference = the chunk's frame in the staging buffer, delivered = the chunk's slot.  hd_key != nullptr (fused chain: the schedule exists
+// in pinned memory only): the kernel brings it to the device as begin_batch_kernel does - a copy would be a blit that waits behind a chip
+// full of compressor waves.
+__global__ __launch_bounds__(256) void plan_gcm_verify_kernel(const tsx_chunk_desc* __restrict__ descs, const uint32_t* __restrict__ zlen, uint64_t mid_stride, uint32_t n,
+                                                              tsx_gcm_chunk* __restrict__ g, const uint4* __restrict__ hd_key, uint4* __restrict__ d_key, uint32_t key_words16) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const tsx_chunk_desc d = descs[i];
+        tsx_gcm_chunk c;
+        c.in_off = (uint64_t)i * mid_stride; c.out_off = d.dst_off; c.len = zlen[i];
+        for (int k = 0; k < 12; k++) c.iv[k] = d.iv[k];
+        c.skip = d.status != TSX_OK ? 1 : d.dst_len != c.len + 28 ? 2 : 0;
+        g[i] = c;
+    }
+    if (hd_key) for (uint32_t k = i; k < key_words16; k += gridDim.x * blockDim.x) d_key[k] = hd_key[k];
+}
+
+// Chunks [sb.lo, sb.lo + sb.n) - a member whose GCM stage has run (in its waves, or in separate_finish) - before anything of them is
+// reported or copied back: gcode[i] = 0 (delivered bytes decrypt to the frame and carry its tag, or the chunk was not TSX_OK anyway),
+// TSX_E_VERIFY, or TSX_E_NOMEM.  Ordinary kernels next to the service, as verify_piece's: the piece counts as a fetch having been seen
+// and waits with the fetch side's safety net.  The test hook verify_damage_out_* acts here, flag or no flag.
+static int gcm_verify_piece(tsx_run& r, const tsx_sub& sb, int32_t* gcode) {
+    tsx_ctx* c = r.c;
+    tsx_device* dev = c->dev;
+    tsx_timing& t = c->timing;
+    const bool verify = (r.flags & TSX_VERIFY_GCM) != 0;
+    const long long dj = g_cfg.verify_damage_out_chunk, doff = g_cfg.verify_damage_out_off;
+    const bool damage = dj >= sb.lo && dj < sb.lo + sb.n && doff >= 0 && c->h_descs[dj].status == TSX_OK && doff < (long long)c->h_descs[dj].dst_len;
+    if (!verify && !damage) return TSX_OK;
+    if (verify) {
+        for (uint32_t i = 0; i < sb.n; i++) gcode[sb.lo + i] = c->h_descs[sb.lo + i].status == TSX_OK ? TSX_E_NOMEM : TSX_OK;
+        bool have_verdicts = false;
+        const int rc = verdicts_reserve(c, (sb.n + ZB_VERDICT_WORDS - 1) / ZB_VERDICT_WORDS, &have_verdicts);      // one word per chunk
+        if (rc || !have_verdicts) return rc;
+        memset(c->h_verdicts, 0, (size_t)sb.n * 4);
+    }
+    svc_foreground_scope fg(dev);
+    HIPCHK(hipEventRecord(c->ev[EV_VERIFY_BEGIN], c->st));
+    if (damage) { hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, c->st, r.d_dst + c->h_descs[dj].dst_off + doff); t.gcm_launches++; }
+    if (verify) {
+        const bool stage_key = r.fuse_stages;                           // (separate stages: separate_finish has uploaded it, run_batch wipes it)
+        const uint32_t kw = (uint32_t)(sizeof(tsx_gcm_key) / 16);
+        if (stage_key) { c->key_staged = true; c->key_wiped = false; }   // (run_batch clears d_key itself when the batch fails before this piece's wipe)
+        hipLaunchKernelGGL(plan_gcm_verify_kernel, dim3(std::max((sb.n + 255u) / 256u, stage_key ? 6u : 1u)), dim3(256), 0, c->st, (const tsx_chunk_desc*)(c->hd_descs + sb.lo),
+                           (const uint32_t*)(c->d_zlen + sb.lo), (uint64_t)c->mid_stride, sb.n, c->d_gchunks + sb.lo, stage_key ? (const uint4*)c->hd_key : (const uint4*)nullptr,
+                           (uint4*)c->d_key, stage_key ? kw : 0u);
+        tsx_launch_gcm_verify(c->st, dev->d_aes, c->d_key, c->d_gchunks + sb.lo, c->hd_descs + sb.lo, sb.n, (uint32_t)tsx_transformed_bound(r.max_len, TSX_COMPRESS),
+                              c->d_mid + (size_t)sb.lo * c->mid_stride, r.d_dst, c->d_partials + (size_t)sb.lo * c->partials_per_chunk, c->hd_verdicts, nullptr);
+        t.gcm_launches += 3;
+        if (stage_key) {                                                // the schedule does not stay on the device between the pieces
+            hipLaunchKernelGGL(wipe_key_kernel, dim3(6), dim3(256), 0, c->st, (uint4*)c->d_key, kw, (uint4*)c->d_keyraw); t.gcm_launches++;
+        }
+    }
+    HIPCHK(hipEventRecord(c->ev[EV_VERIFY_END], c->st));
+    HIPCHK(wait_event_watching(c, c->ev[EV_VERIFY_END]));
+    if (verify) {
+        if (r.fuse_stages) c->key_wiped = true;
+        t.gcm_ms += ev_ms(c->ev[EV_VERIFY_BEGIN], c->ev[EV_VERIFY_END]);
+        for (uint32_t i = 0; i < sb.n; i++)                             // (a chunk that was TSX_OK and has no verdict has not been examined: not reported TSX_OK)
+            if (c->h_descs[sb.lo + i].status == TSX_OK) gcode[sb.lo + i] = c->h_verdicts[i] == TSX_GV_SEEN ? TSX_OK : TSX_E_VERIFY;
     }
     HIPCHK(hipGetLastError());
     return TSX_OK;
@@ -528,6 +606,8 @@ static int run_compress(tsx_run& r) {
     c->verify_block_form = 0; c->verify_fallback = 0;
     std::vector<int32_t> vcode;                                         // TSX_VERIFY: per chunk, what the verifier has to say (0: nothing)
     if (r.flags & TSX_VERIFY) vcode.assign(n, 0);
+    std::vector<int32_t> gcode;                                         // TSX_VERIFY_GCM: the same of the GCM verifier
+    if (r.flags & TSX_VERIFY_GCM) gcode.assign(n, 0);
     // ---- the pieces ----
     std::vector<tsx_sub> subs;
     {
@@ -615,6 +695,10 @@ static int run_compress(tsx_run& r) {
         if (!vcode.empty() && (rc = verify_piece(r, sb, self_status, vcode.data()))) return abandon_all(rc);
         if (!self_status && (rc = separate_finish(r, sb, k == 0))) return abandon_all(rc);
         if (!vcode.empty()) for (uint32_t i = sb.lo; i < sb.lo + sb.n; i++) if (vcode[i] && c->h_descs[i].status == TSX_OK) { c->h_descs[i].status = vcode[i]; c->h_descs[i].dst_len = 0; }
+        // verify on upload, GCM stage: the piece's delivered bytes, before its descriptors reach the caller and before copy_back / pack_chunks
+        // move them (chunks the Zstandard verifier has just failed are skipped)
+        if (r.enc && (rc = gcm_verify_piece(r, sb, gcode.data()))) return abandon_all(rc);
+        if (!gcode.empty()) for (uint32_t i = sb.lo; i < sb.lo + sb.n; i++) if (gcode[i] && c->h_descs[i].status == TSX_OK) { c->h_descs[i].status = gcode[i]; c->h_descs[i].dst_len = 0; }
         memcpy(r.descs + sb.lo, c->h_descs + sb.lo, (size_t)sb.n * sizeof(tsx_chunk_desc));
         if (r.zc_dst) {
             // the bytes are where they belong; a packed batch is packed down in place.  (compress_zero_copy_ok: dst_size >= out_bytes, the
@@ -674,8 +758,21 @@ static int launch_stages(const tsx_run& r, const tsx_sub& sb, hipEvent_t* e, hip
         if (flags & TSX_CRC) { tsx_launch_crc32c(st, c->dev->d_crc, r.d_src, dd, n, r.max_len, dpart, 0); t.crc_launches += 2; }
         HIPCHK(hipEventRecord(e[SUB_STAGE1], st));
         HIPCHK(hipEventRecord(e[SUB_STAGE2], st));
-        if (r.enc) launch_gcm_stage(r, st, lo, n, 0, 0, 0, r.max_len, r.d_src, r.d_dst);
-        else launch_copy_chunks(r, st, lo, n, 0, r.d_src);
+        if (r.enc) {
+            launch_gcm_stage(r, st, lo, n, 0, 0, 0, r.max_len, r.d_src, r.d_dst);
+            // test hook verify_damage_out_*: an encrypt-only chunk that fits its slot delivers src_len + 28 bytes
+            const long long dj = g_cfg.verify_damage_out_chunk, doff = g_cfg.verify_damage_out_off;
+            if (dj >= lo && dj < lo + n && doff >= 0 && doff < (long long)r.descs[dj].src_len + 28 && (uint64_t)r.descs[dj].src_len + 28 <= r.descs[dj].dst_cap) {
+                hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, st, r.d_dst + r.descs[dj].dst_off + doff); t.gcm_launches++;
+            }
+            // verify on upload, GCM stage: in stream behind the stage, on the work items plan_gcm_kernel has made (in: the source chunk on the
+            // device, out: where the chunk was delivered - with zero-copy output the caller's buffer); a chunk that fails is TSX_E_VERIFY in
+            // d_status before publish_status_kernel reports it
+            if (flags & TSX_VERIFY_GCM) {
+                tsx_launch_gcm_verify(st, c->dev->d_aes, c->d_key, c->d_gchunks + lo, dd, n, r.max_len, r.d_src, r.d_dst, dpart, nullptr, ds);
+                t.gcm_launches += 2;
+            }
+        } else launch_copy_chunks(r, st, lo, n, 0, r.d_src);
         hipLaunchKernelGGL(publish_status_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dd, (const int32_t*)ds, n, hm);
     } else {
         HIPCHK(hipEventRecord(e[SUB_STAGE1], st));
@@ -874,11 +971,13 @@ int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs,
     const bool packed = mem_kind == TSX_MEM_HOST_PACKED;
     if (packed && mode != 0) return TSX_E_INVAL;
     uint32_t flags = mode == 2 ? TSX_CRC : params->flags;
-    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC | TSX_ZSTD_CHECKSUM | TSX_VERIFY)) return TSX_E_INVAL;
+    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC | TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM)) return TSX_E_INVAL;
     // the content checksum is the compressor's to write; a decoder verifies whatever frame declares one, asked or not.  Verify on upload
     // reads back what the compressor wrote: both modify TSX_COMPRESS on transform and mean nothing anywhere else
     if (mode == 0 && (flags & (TSX_ZSTD_CHECKSUM | TSX_VERIFY)) && !(flags & TSX_COMPRESS)) return TSX_E_INVAL;
-    if (mode != 0) flags &= ~(TSX_ZSTD_CHECKSUM | TSX_VERIFY);
+    // ... and the GCM verifier reads back what the GCM stage wrote: a modifier of TSX_ENCRYPT on transform
+    if (mode == 0 && (flags & TSX_VERIFY_GCM) && !(flags & TSX_ENCRYPT)) return TSX_E_INVAL;
+    if (mode != 0) flags &= ~(TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM);
     if (mode != 2) {
         if (params->aad_len > 64) return TSX_E_INVAL;
         if ((flags & TSX_COMPRESS) && !(params->zstd_level >= 0 && params->zstd_level <= 3)) return TSX_E_UNSUPPORTED;   // 0 = 3 (the library default), 1, 2, 3
@@ -893,7 +992,7 @@ int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs,
     r.enc = mode != 2 && (flags & TSX_ENCRYPT); r.comp = mode != 2 && (flags & TSX_COMPRESS);
     r.fuse_stages = r.comp && !g_cfg.stages_separate;
     const bool service = mode == 0 && r.comp;
-    c->key_wiped = false;
+    c->key_wiped = false; c->key_staged = false;
     // every batch of ordinary kernels claims the reserved CUs for its duration (+ fetch_quiet_ms); a fused compressing batch queues none
     svc_foreground_scope fg(service && r.fuse_stages ? nullptr : c->dev);
     const int rc = service ? run_compress(r) : run_batch_inner(r);
@@ -904,6 +1003,11 @@ int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs,
         // nothing of the key was uploaded (every wave took and wiped its own copy of the schedule); what is left is the pinned original,
         // and run_compress returns only when none of the batch's members can still be running
         if (r.enc) ctx_wipe_host_key(c);
+        if (c->key_staged && !c->key_wiped) {
+            // the GCM verifier had brought the schedule to the device and the batch failed before its wipe kernel was queued
+            hipMemcpyAsync(c->d_key, c->dev->h_zeros, sizeof(tsx_gcm_key), hipMemcpyHostToDevice, c->st);
+            hipStreamSynchronize(c->st);
+        }
         if (rc != TSX_OK) (void)hipGetLastError();
         return rc;
     }

@@ -64,7 +64,8 @@ struct tsx_ctx {
     uint32_t last_members = 0;                     // members the last compressing batch went as (test hook)
     bool last_zero_copy = false;                   // ... and whether its waves wrote into the caller's buffer (test hook)
     bool key_wiped = false;                        // the batch's own wipe_key_kernel has cleared d_key / d_keyraw
-    // verify on upload (TSX_VERIFY): the verifier's words per chunk of a slice, pinned, and as the device addresses them (created by the first verifying batch)
+    bool key_staged = false;                       // a fused compressing batch's GCM verifier has brought the key schedule to d_key (wiped behind every piece)
+    // verify on upload (TSX_VERIFY, and TSX_VERIFY_GCM of a compressing batch): the verifier's words per chunk of a slice, pinned, and as the device addresses them (created by the first verifying batch)
     uint32_t* h_verdicts = nullptr; uint32_t* hd_verdicts = nullptr; size_t verdicts_cap = 0;
     uint32_t verify_block_form = 0, verify_fallback = 0;   // chunks of the last batch the block form judged / that were decoded in full (test hook)
 };

@@ -41,6 +41,9 @@ struct tsx_cfg {
     // verify on upload (TSX_VERIFY): XOR 1 into byte `off` of chunk `chunk` of the batch (-1: none) - of the device copy of its source (put back
     // behind the verification), of its frame in the staging buffer - after the chunk's member has completed and before it is verified
     long long verify_damage_src_chunk = -1, verify_damage_src_off = 0, verify_damage_frame_chunk = -1, verify_damage_frame_off = 0;
+    // verify on upload, GCM stage (TSX_VERIFY_GCM): XOR 1 into byte `off` of that chunk's delivered IV || C || TAG, through the device's view of the
+    // destination, behind the GCM stage and in front of the GCM verifier - whether or not the flag is set (-1: none; an offset beyond dst_len: nothing)
+    long long verify_damage_out_chunk = -1, verify_damage_out_off = 0;
     uint32_t verify_slice_chunks = 0;     // chunks per slice of the verifier's workspace (0 = as many as fit its byte budget)
     bool verify_force_fallback = false;   // every chunk is decoded in full and compared (phase two), none by the block form
 };

@@ -193,3 +193,18 @@ void tsx_launch_gcm_setup(hipStream_t st, const tsx_aes_tables* d_aes, const uin
 void tsx_launch_gcm(hipStream_t st, const tsx_aes_tables* d_aes, const tsx_gcm_key* d_key, const tsx_gcm_chunk* d_chunks, uint32_t n,
                     uint32_t max_len, const uint8_t* in, uint8_t* out, uint32_t* d_partials, int32_t* d_status,
                     int decrypt);
+
+// Verify on upload, GCM stage (TSX_VERIFY_GCM): for chunk i the delivered bytes delivered + d_chunks[i].out_off (IV || C || TAG as the
+// device wrote them: device memory, or the caller's registered host buffer) against the reference plaintext ref + d_chunks[i].in_off of
+// d_chunks[i].len bytes and against descs[i] (iv, dst_len).  d_chunks[i].skip: 0 = examine, 1 = the chunk had failed before (verdict 0),
+// 2 = its dst_len is not len + 28 (fails without being read).  The result goes to verdicts[i] (any memory the device addresses; may be
+// nullptr) and, for a chunk that fails, as TSX_E_VERIFY to d_status[i] (may be nullptr).  d_partials: n * max_sub * 5 u32.  Two kernels.
+// What a chunk's verdict word says (gcm_verify_final_kernel): TSX_GV_SEEN alone = verified; any other bit = why not.
+#define TSX_GV_SEEN   1u    /* the chunk was TSX_OK and has been examined */
+#define TSX_GV_LEN    2u    /* dst_len != plaintext length + 28 */
+#define TSX_GV_IV     4u    /* the delivered IV is not the descriptor's */
+#define TSX_GV_PLAIN  8u    /* AES-CTR of the delivered ciphertext is not the reference plaintext */
+#define TSX_GV_TAG    16u   /* GHASH(AAD, delivered ciphertext, lengths) xor E_K(J0) is not the delivered tag */
+void tsx_launch_gcm_verify(hipStream_t st, const tsx_aes_tables* d_aes, const tsx_gcm_key* d_key, const tsx_gcm_chunk* d_chunks,
+                           const tsx_chunk_desc* descs, uint32_t n, uint32_t max_len, const uint8_t* ref, const uint8_t* delivered,
+                           uint32_t* d_partials, uint32_t* verdicts, int32_t* d_status);

@@ -456,13 +456,14 @@ Bytes BaseTransformChunkEnumeration::nextElement() {
 
 GpuTransformChunkEnumeration::GpuTransformChunkEnumeration(std::shared_ptr<Backend> be, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                                            std::optional<DataKeyAndAAD> enc, IvSupplier iv, int batchChunks, bool withCrc, uint32_t profile, bool readAhead,
-                                                           int zstdLevel, bool zstdChecksum, bool zstdVerify)
+                                                           int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify)
     : be_(std::move(be)), inner_(std::move(inner)), compress_(compress), enc_(std::move(enc)), iv_(std::move(iv)), batch_(batchChunks), withCrc_(withCrc),
-      profile_(profile), readAhead_(readAhead), level_(zstdLevel), checksum_(zstdChecksum), verify_(zstdVerify) {
+      profile_(profile), readAhead_(readAhead), level_(zstdLevel), checksum_(zstdChecksum), verify_(zstdVerify), gcmVerify_(gcmVerify) {
     if (!inner_) throw std::invalid_argument("inner cannot be null");
     if (level_ < 0 || level_ > 3) throw std::invalid_argument("zstd level must be 1, 2 or 3 (0 = library default), " + std::to_string(level_) + " given");
     if (checksum_ && !compress_) throw std::invalid_argument("zstd checksum needs compression");
     if (verify_ && !compress_) throw std::invalid_argument("zstd verification needs compression");
+    if (gcmVerify_ && !enc_) throw std::invalid_argument("GCM verification needs encryption");
     if (batch_ < 1) throw std::invalid_argument("batchChunks must be positive");
     if (enc_ && enc_->dataKey.size() != 32) throw std::invalid_argument("AES-256 data key must be 32 bytes");
     // CompressionChunkEnumeration.java:39-42 (null) then EncryptionChunkEnumeration.java:41-47 (inner + ivSize + getOutputSize)
@@ -479,7 +480,7 @@ GpuTransformChunkEnumeration::Batch GpuTransformChunkEnumeration::transformNextB
     std::vector<Bytes> in;
     while ((int)in.size() < batch_ && inner_->hasMoreElements()) in.push_back(inner_->nextElement());
     if (in.empty()) return out;
-    const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u);
+    const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u);
     if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !withCrc_) { out.chunks = std::move(in); return out; }     // pure base: nothing to do
     std::vector<tsx_chunk_desc> d(in.size());
     size_t so = 0, dofs = 0;
@@ -517,7 +518,7 @@ GpuTransformChunkEnumeration::PackedBatch GpuTransformChunkEnumeration::transfor
     std::vector<Bytes> in;
     while ((int)in.size() < batch_ && inner_->hasMoreElements()) in.push_back(inner_->nextElement());
     if (in.empty()) return out;
-    const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u);
+    const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u);
     if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0) {                   // pure base: the chunks are the object
         for (const Bytes& c : in) {
             out.object.insert(out.object.end(), c.begin(), c.end());

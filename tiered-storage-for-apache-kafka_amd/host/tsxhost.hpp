@@ -247,7 +247,7 @@ public:
     GpuTransformChunkEnumeration(std::shared_ptr<Backend> backend, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                  std::optional<DataKeyAndAAD> encryption, IvSupplier ivSupplier = secureRandomIvSupplier(),
                                  int batchChunks = 64, bool withCrc = false, uint32_t zstdProfile = TSX_ZSTD_PROFILE_1_5_7, bool readAhead = true,
-                                 int zstdLevel = 0, bool zstdChecksum = false, bool zstdVerify = false);
+                                 int zstdLevel = 0, bool zstdChecksum = false, bool zstdVerify = false, bool gcmVerify = false);
     ~GpuTransformChunkEnumeration() override;
     // Zstandard level of the frames (compression.zstd.level): 0 = the library default (3, what the reference uses), 1, 2 or 3;
     // anything else is refused here, not at the first batch
@@ -259,6 +259,10 @@ public:
     // the chunk is handed on; a chunk whose frame does not restore it (TSX_E_VERIFY) raises what any failed chunk raises.  Covers the
     // frame, not the encryption behind it.  Refused here when the chain does not compress.
     bool zstdVerify() const { return verify_; }
+    // verify on upload, AES-GCM stage (encryption.verify, TSX_VERIFY_GCM): the IV || C || TAG the device has delivered for a chunk is decrypted
+    // and authenticated on the device, against the bytes that went into the stage, before the chunk is handed on; a chunk that fails
+    // (TSX_E_VERIFY) raises what any failed chunk raises.  Refused here when the chain does not encrypt.
+    bool gcmVerify() const { return gcmVerify_; }
     int originalChunkSize() const override { return inner_->originalChunkSize(); }
     std::optional<int> transformedChunkSize() const override { return transformedChunkSize_; }
     bool hasMoreElements() override;
@@ -290,6 +294,7 @@ private:
     int level_;
     bool checksum_;
     bool verify_;
+    bool gcmVerify_;
     std::optional<int> transformedChunkSize_;
     std::vector<Bytes> ready_;
     size_t next_ = 0;
@@ -340,6 +345,7 @@ public:
     int zstdLevel() const { return inner_->zstdLevel(); }   // the enumeration's (the finisher transforms through it)
     bool zstdChecksum() const { return inner_->zstdChecksum(); }
     bool zstdVerify() const { return inner_->zstdVerify(); }
+    bool gcmVerify() const { return inner_->gcmVerify(); }
 
 private:
     bool nextBatch();

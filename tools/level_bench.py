@@ -8,7 +8,11 @@ transformed / original, and the compressor service's kernel time; a sample of ev
 way; the frames with one are checked against libzstd's own ZSTD_c_checksumFlag frames.
 --verify: the same for verify on upload (TSX_VERIFY): every level without and with it, alternating (off on, on off, ... in one process); the
 rows of the verifying runs carry the verifier's own time of the last batch (tsx_timing.unzstd_ms, unzstd_launches).
-  python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8] [--levels 3] [--checksum] [--verify]"""
+--verify-gcm: the same for the GCM stage's verify on upload (TSX_VERIFY_GCM): off on, on off in one process; the verifying runs' rows carry
+the GCM stage's time and launches of the last batch (tsx_timing.gcm_ms, gcm_launches: the verifier's, the waves encrypt their own frames).
+The rows are appended to --out as well (default with --verify-gcm: profiles/gcm_verify_level_bench.jsonl).
+  python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8] [--levels 3] [--checksum] [--verify]
+                              [--verify-gcm] [--out FILE]"""
 import argparse
 import ctypes
 import json
@@ -42,7 +46,18 @@ def main():
     ap.add_argument("--levels", default="1,2,3")
     ap.add_argument("--checksum", action="store_true", help="each level with and without TSX_ZSTD_CHECKSUM, alternating")
     ap.add_argument("--verify", action="store_true", help="each level without and with TSX_VERIFY, alternating")
+    ap.add_argument("--verify-gcm", action="store_true", help="each level without and with TSX_VERIFY_GCM, alternating")
+    ap.add_argument("--out", default=None, help="append every JSON line to this file as well")
     args = ap.parse_args()
+    if args.verify_gcm and not args.out:
+        args.out = os.path.join(ROOT, "profiles", "gcm_verify_level_bench.jsonl")
+
+    def emit(obj):
+        line = json.dumps(obj)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
 
     import torch  # before libtsxform: one shared HIP runtime
     import tsxform
@@ -55,8 +70,8 @@ def main():
     n = args.segments * cps
     T = args.callers
     flags = nat.COMPRESS | nat.ENCRYPT | nat.CRC
-    levels = [(int(x), ck, vf) for x in args.levels.split(",") for ck in ((False, True) if args.checksum else (False,))
-              for vf in ((False, True) if args.verify else (False,))]
+    levels = [(int(x), ck, vf, gv) for x in args.levels.split(",") for ck in ((False, True) if args.checksum else (False,))
+              for vf in ((False, True) if args.verify else (False,)) for gv in ((False, True) if args.verify_gcm else (False,))]
 
     def libzstd_frame(raw, level, checksum):
         """libzstd's frame as oracle/zstd_ref.c makes it, with ZSTD_c_checksumFlag on request."""
@@ -114,8 +129,8 @@ def main():
         order = []
         for r in range(args.rounds):
             order += levels if r % 2 == 0 else levels[::-1]
-        for level, ck, vf in order:
-            p = nat.Native.make_params(flags | (nat.ZSTD_CHECKSUM if ck else 0) | (nat.VERIFY if vf else 0), synth.KEY, synth.AAD, zstd_level=level)
+        for level, ck, vf, gv in order:
+            p = nat.Native.make_params(flags | (nat.ZSTD_CHECKSUM if ck else 0) | (nat.VERIFY if vf else 0) | (nat.VERIFY_GCM if gv else 0), synth.KEY, synth.AAD, zstd_level=level)
             ds = [d.copy() for _ in range(T)]
 
             def step(t):
@@ -148,20 +163,20 @@ def main():
                 exp = o.gcm_encrypt_chunk(synth.KEY, ds[0]["iv"][i].tobytes(), synth.AAD, libzstd_frame(raw, level, ck))
                 ok = ok and got == exp
             tm = N.ctx_timing(ctxs[0])
-            row = {"content": content, "level": level, "checksum": ck, "verify": vf, "unzstd_ms": round(tm.unzstd_ms, 2), "unzstd_launches": tm.unzstd_launches, "gibs": round(args.steps * n * CH / GiB / el, 3), "elapsed_s": round(el, 3),
+            row = {"content": content, "level": level, "checksum": ck, "verify": vf, "verify_gcm": gv, "gcm_ms": round(tm.gcm_ms, 2), "gcm_launches": tm.gcm_launches, "unzstd_ms": round(tm.unzstd_ms, 2), "unzstd_launches": tm.unzstd_launches, "gibs": round(args.steps * n * CH / GiB / el, 3), "elapsed_s": round(el, 3),
                    "ratio": round(float(ds[0]["dst_len"].astype(np.int64).sum() - 28 * n) / (n * CH), 4),
                    "kernel_ms": round(s1["kernel_ms"] - s0["kernel_ms"], 1), "launches": s1["launches"] - s0["launches"],
                    "chunks": n, "distinct_chunks": distinct, "steps": args.steps, "callers": T,
                    "checked_chunks": len(sample), "exact_vs_libzstd": bool(ok), "generated_in_s": round(gen_s, 1)}
             rows.append(row)
-            print(json.dumps(row), flush=True)
+            emit(row)
     summary = {}
     for r in rows:
-        k = "%s_L%d%s%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else "", "_verify" if r["verify"] else "")
+        k = "%s_L%d%s%s%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else "", "_verify" if r["verify"] else "", "_verify_gcm" if r["verify_gcm"] else "")
         summary.setdefault(k, []).append(r["gibs"])
-    print(json.dumps({"metric": "GiB/s of original bytes per level (runs in order)", "runs": summary,
-                      "ratio": {"%s_L%d%s%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else "", "_verify" if r["verify"] else ""): r["ratio"] for r in rows},
-                      "all_exact": all(r["exact_vs_libzstd"] for r in rows), "libzstd": o.zstd_version(), "tsxform": N.version()}), flush=True)
+    emit({"metric": "GiB/s of original bytes per level (runs in order)", "runs": summary,
+                      "ratio": {"%s_L%d%s%s%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else "", "_verify" if r["verify"] else "", "_verify_gcm" if r["verify_gcm"] else ""): r["ratio"] for r in rows},
+                      "all_exact": all(r["exact_vs_libzstd"] for r in rows), "libzstd": o.zstd_version(), "tsxform": N.version()})
 
 
 if __name__ == "__main__":
