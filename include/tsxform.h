@@ -75,6 +75,23 @@ extern "C" {
  * packed batch that is packed down in place; a common-mode error of the AES and GHASH device functions, which the encrypting and the
  * verifying kernels share (the test suite's comparison with OpenSSL guards those).  (0x10 and 0x40 stay unassigned.) */
 #define TSX_VERIFY_GCM 0x80u
+/* Modifier of a transform with any stage combination: validate the SOURCE as a Kafka log before it is uploaded.  The batch's chunks,
+ * concatenated in descriptor order ([src_off, src_off + src_len) of chunk 0, 1, ...; gaps between slots are not part of it, chunks of
+ * length 0 contribute nothing), are taken as ONE byte stream that begins on a record-batch boundary and ends on one - a whole segment in
+ * one call; a segment split over several calls is out of scope.  Every batch of the stream is checked on the device the way
+ * DefaultRecordBatch.ensureValid() plus a walk over the log would check it (fields big-endian: baseOffset @0, batchLength @8,
+ * partitionLeaderEpoch @12, magic @16, crc @17, attributes @21 ...):
+ *   at least 61 bytes are left in the stream; batchLength >= 49 as a signed 32-bit value; position + 12 + batchLength <= the stream's
+ *   length; magic == 2; CRC32C (java.util.zip.CRC32C) over [position + 21, position + 12 + batchLength) equals the crc field; the stream
+ *   ends exactly at the end of a batch.  (Bytes 0..15 are outside the CRC: damage there, other than to the length, does not fail.)
+ * The first invalid batch decides: the chunk that holds its first byte, and every chunk after it, get status TSX_E_RECORDS and dst_len 0
+ * (a chunk that already carries another error keeps it); earlier chunks are delivered; the call returns TSX_OK, as with TSX_VERIFY.  With
+ * the flag set no chunk is reported TSX_OK whose bytes the validator has not covered (TSX_E_NOMEM when it finds no memory).  The
+ * validator's kernels are ordinary kernels that run while the batch's own stages do (next to the compressor service the batch counts as
+ * a fetch having been seen); tsx_ctx_records() describes what they found.  With the flag clear nothing is allocated or launched.
+ * NOT covered: the framing of the records inside a batch, the order of offsets, compressed payloads; message sets of magic 0 / 1 fail
+ * (reason 3).  Detransform accepts and ignores the flag.  (0x10 and 0x40 stay unassigned.) */
+#define TSX_VALIDATE_RECORDS 0x100u
 
 /* where src/dst live */
 /* host pointers.  The batch is cut into pieces whose H2D copy, kernels and D2H copy overlap: pieces of >= 64 MiB in order on three
@@ -113,6 +130,7 @@ extern "C" {
 #define TSX_E_SHORT_CHUNK   -8  /* encrypted chunk shorter than IV+TAG                            */
 #define TSX_E_UNSUPPORTED   -9
 #define TSX_E_VERIFY        -10 /* TSX_VERIFY / TSX_VERIFY_GCM: the frame written for this chunk does not restore it (per chunk)  */
+#define TSX_E_RECORDS       -11 /* TSX_VALIDATE_RECORDS: the source holds an invalid record batch in or before this chunk (per chunk) */
 
 /* Per-chunk descriptor; mirrors io.aiven.kafka.tieredstorage.Chunk (core/.../Chunk.java:21-36:
  * id, originalPosition, originalSize, transformedPosition, transformedSize) with the in/out split
@@ -134,7 +152,7 @@ typedef struct tsx_chunk_desc {
 /* Per-batch parameters: one (data key, AAD) pair per segment
  * (AesEncryptionProvider.createDataKeyAndAAD, core/.../security/AesEncryptionProvider.java:52-58). */
 typedef struct tsx_batch_params {
-    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC [| TSX_ZSTD_CHECKSUM] [| TSX_VERIFY] [| TSX_VERIFY_GCM] */
+    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC [| TSX_ZSTD_CHECKSUM] [| TSX_VERIFY] [| TSX_VERIFY_GCM] [| TSX_VALIDATE_RECORDS] */
     uint32_t aad_len;      /* reference: 32                                                         */
     uint8_t  key[32];      /* AES-256 data key (SecretKey.getEncoded())                             */
     uint8_t  aad[64];
@@ -217,6 +235,21 @@ int  tsx_device_count(void);
 int  tsx_ctx_create(int device_index, uint32_t max_chunks, uint32_t max_chunk_size, tsx_ctx** out);
 void tsx_ctx_destroy(tsx_ctx* ctx);
 int  tsx_ctx_timing(const tsx_ctx* ctx, tsx_timing* out);
+/* What TSX_VALIDATE_RECORDS found in the last batch on a ctx (explicit contexts only; all zero, first_bad_pos UINT64_MAX, when that
+ * batch did not validate). */
+typedef struct tsx_records_info {
+    uint64_t batches;             /* valid batches in front of the first invalid one (all of them in a clean stream)                 */
+    uint64_t compressed_batches;  /* ... of which attributes & 7 != 0 (what compression.heuristic.enabled asks, for the whole segment) */
+    uint64_t first_bad_pos;       /* stream offset of the first invalid batch, or UINT64_MAX                                         */
+    uint32_t first_bad_reason;    /* 0 none; 1 truncated (fewer than 61 bytes left, or the batch reaches beyond the stream's end);
+                                     2 length (batchLength < 49); 3 magic; 4 crc                                                     */
+    uint32_t repaired_chunks;     /* chunks whose batches the resolver walked itself: the chunk's own walker had found no entry, or
+                                     another one than the chain arrives at (a CRC-valid batch inside a record value, a damaged first
+                                     batch)                                                                                          */
+    float    ms;                  /* the validator's kernels, by events                                                              */
+    uint32_t reserved_;
+} tsx_records_info;
+int  tsx_ctx_records(const tsx_ctx* ctx, tsx_records_info* out);
 int  tsx_ctx_device(const tsx_ctx* ctx);                /* device index (0 .. tsx_device_count()-1) the ctx lives on */
 
 /* Device of the calling thread's ctx-less calls: 0 .. tsx_device_count()-1, or -1 = automatic (least loaded).  The JVM side

@@ -39,6 +39,7 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
     private final boolean zstdChecksum;      // content checksum in every frame
     private final boolean zstdVerify;        // every frame is read back on the device and compared with its chunk
     private final boolean gcmVerify;         // every delivered IV || C || TAG is decrypted and authenticated on the device
+    private final boolean recordsValidate;   // the source, as one stream, is walked on the device as a Kafka v2 log
     private final int device;
     private final Integer transformedChunkSize;
     private final ArrayDeque<byte[]> ready = new ArrayDeque<>();
@@ -138,7 +139,27 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
                                         final SecureRandom random, final int zstdProfile, final int segmentHash,
                                         final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
                                         final boolean zstdVerify, final boolean gcmVerify) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, readAhead, zstdLevel,
+            zstdChecksum, zstdVerify, gcmVerify, false);
+    }
+
+    /**
+     * @param recordsValidate validate the source before it is uploaded, plugin configuration key {@code segment.records.validate}
+     *                  (INTEGRATION.md 2), default false: the segment's bytes, as ONE stream, are walked on the device as a Kafka v2 log
+     *                  (length, magic and CRC32C of every record batch: DefaultRecordBatch.ensureValid() for the whole file, where
+     *                  SegmentCompressionChecker looks at the first batch).  The chunk in which the first invalid batch begins, and every
+     *                  chunk behind it, fail ({@link TsxNative#E_RECORDS}, raised like any failed chunk): the segment copy fails and the
+     *                  broker keeps the local segment.  The whole segment must fit ONE batch ({@code batchChunks} x chunk size): a segment
+     *                  that does not is refused with an IllegalStateException, never validated in part.  Log segments only - not the
+     *                  index files; message sets of magic 0 / 1 fail: leave it off for such topics.
+     */
+    public GpuTransformChunkEnumeration(final TransformChunkEnumeration inner, final boolean compress,
+                                        final DataKeyAndAAD keyAndAad, final int batchChunks,
+                                        final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                        final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
+                                        final boolean zstdVerify, final boolean gcmVerify, final boolean recordsValidate) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
+        this.recordsValidate = recordsValidate;
         if (zstdChecksum && !compress) {
             throw new IllegalArgumentException("Zstd checksum needs compression");
         }
@@ -248,10 +269,15 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
         if (in.isEmpty()) {
             return out;
         }
+        if (recordsValidate && inner.hasMoreElements()) {
+            throw new IllegalStateException("segment.records.validate: the whole segment must fit one batch (batchChunks x chunk size = "
+                + batchChunks + " x " + inner.originalChunkSize() + " bytes); it is not validated in part");
+        }
         final int flags = (compress ? TsxNative.COMPRESS : 0) | (keyAndAad != null ? TsxNative.ENCRYPT : 0)
             | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0)
             | (zstdVerify ? TsxNative.VERIFY : 0)
-            | (gcmVerify ? TsxNative.VERIFY_GCM : 0);
+            | (gcmVerify ? TsxNative.VERIFY_GCM : 0)
+            | (recordsValidate ? TsxNative.VALIDATE_RECORDS : 0);
         // per-thread, reused, pinned (registered with the device): the compressor waves write every chunk's IV || C || TAG straight into the
         // dst buffer's slots (zero-copy output, DESIGN.md section 1) - a pageable buffer would send the batch through copy engines instead.
         // Footprint per thread: ~2.1 GiB at 256 x 4 MiB (source batch + bound-sized output slots), INTEGRATION.md section 4.

@@ -29,6 +29,13 @@ public final class TsxNative {
      * ignores the flag.
      */
     public static final int VERIFY_GCM = 0x80;
+    /**
+     * On transform, with any chain: validate the source ({@code segment.records.validate}).  The batch's chunks, in order, are ONE stream
+     * that begins and ends on a record-batch boundary - a whole log segment; every v2 record batch of it is checked on the device (length,
+     * magic, CRC32C) before the chunks are reported.  The chunk in which the first invalid batch begins, and every chunk behind it, have
+     * status {@link #E_RECORDS}.  Detransform accepts and ignores the flag.
+     */
+    public static final int VALIDATE_RECORDS = 0x100;
 
     public static final int OK = 0;
     public static final int E_TAG_MISMATCH = -5;
@@ -36,6 +43,8 @@ public final class TsxNative {
     public static final int E_BAD_SIZE = -7;
     /** Under {@link #VERIFY} / {@link #VERIFY_GCM}: what was written for this chunk does not restore it (per chunk; the batch call itself succeeds). */
     public static final int E_VERIFY = -10;
+    /** Under {@link #VALIDATE_RECORDS}: an invalid record batch begins in or before this chunk of the source (per chunk; the batch call itself succeeds). */
+    public static final int E_RECORDS = -11;
 
     /** Size of one tsx_chunk_desc (include/tsxform.h), written/read through a direct little-endian ByteBuffer. */
     public static final int DESC_BYTES = 48;

@@ -16,10 +16,12 @@ COMPRESS, ENCRYPT, CRC = 1, 2, 4
 ZSTD_CHECKSUM = 8        # with COMPRESS on transform: frames carry a content checksum (TSX_ZSTD_CHECKSUM); every fetch verifies one that is there
 VERIFY = 0x20            # with COMPRESS on transform: every frame is read back and compared with its chunk before it is reported (TSX_VERIFY)
 VERIFY_GCM = 0x80        # with ENCRYPT on transform: the delivered IV||C||TAG of every chunk is decrypted and authenticated on the device before it is reported (TSX_VERIFY_GCM)
+VALIDATE_RECORDS = 0x100 # on transform: the batch's source, as ONE stream, is walked on the device as a Kafka v2 log before it is reported (TSX_VALIDATE_RECORDS)
 MEM_HOST, MEM_DEVICE, MEM_HOST_PACKED = 0, 1, 2
 OK, E_INVAL, E_DEVICE, E_NOMEM, E_DST_TOO_SMALL, E_TAG_MISMATCH, E_BAD_FRAME, E_BAD_SIZE, E_SHORT_CHUNK, E_UNSUPPORTED = \
     0, -1, -2, -3, -4, -5, -6, -7, -8, -9
 E_VERIFY = -10           # per chunk, under VERIFY: the frame written for the chunk does not restore it
+E_RECORDS = -11          # per chunk, under VALIDATE_RECORDS: an invalid record batch begins in or before this chunk
 ZSTD_PROFILE_1_5_6, ZSTD_PROFILE_1_5_7 = 0, 1
 ABI_VERSION = 4          # TSX_ABI_VERSION of include/tsxform.h these prototypes were written against
 
@@ -39,6 +41,12 @@ class Timing(C.Structure):
                 ("zstd_ms", C.c_float), ("gcm_ms", C.c_float), ("unzstd_ms", C.c_float),
                 ("crc_launches", C.c_uint32), ("zstd_launches", C.c_uint32), ("gcm_launches", C.c_uint32),
                 ("unzstd_launches", C.c_uint32)]
+
+
+class RecordsInfo(C.Structure):
+    """tsx_records_info of include/tsxform.h: what VALIDATE_RECORDS found in the last batch on a context."""
+    _fields_ = [("batches", C.c_uint64), ("compressed_batches", C.c_uint64), ("first_bad_pos", C.c_uint64), ("first_bad_reason", C.c_uint32),
+                ("repaired_chunks", C.c_uint32), ("ms", C.c_float), ("reserved_", C.c_uint32)]
 
 
 class Config(C.Structure):
@@ -65,7 +73,7 @@ EXPORTS = ["tsx_abi_version", "tsx_version", "tsx_strerror", "tsx_init", "tsx_sh
            "tsx_ctx_create", "tsx_ctx_destroy", "tsx_ctx_timing", "tsx_transformed_bound", "tsx_transform_batch",
            "tsx_detransform_batch", "tsx_crc32c_batch", "tsx_device_malloc", "tsx_device_free", "tsx_memcpy_h2d",
            "tsx_memcpy_d2h", "tsx_ctx_device", "tsx_set_thread_device", "tsx_pool_stats", "tsx_host_register", "tsx_host_unregister",
-           "tsx_init_ex", "tsx_service_stats", "tsx_service_quiesce"]
+           "tsx_init_ex", "tsx_service_stats", "tsx_service_quiesce", "tsx_ctx_records"]
 
 
 class TsxError(RuntimeError):
@@ -101,6 +109,7 @@ class Native:
         L.tsx_ctx_create.restype = C.c_int; L.tsx_ctx_create.argtypes = [C.c_int, u32, u32, C.POINTER(vp)]
         L.tsx_ctx_destroy.restype = None; L.tsx_ctx_destroy.argtypes = [vp]
         L.tsx_ctx_timing.restype = C.c_int; L.tsx_ctx_timing.argtypes = [vp, C.POINTER(Timing)]
+        L.tsx_ctx_records.restype = C.c_int; L.tsx_ctx_records.argtypes = [vp, C.POINTER(RecordsInfo)]
         L.tsx_transformed_bound.restype = sz; L.tsx_transformed_bound.argtypes = [sz, u32]
         for name in ("tsx_transform_batch", "tsx_detransform_batch"):
             f = getattr(L, name); f.restype = C.c_int
@@ -187,6 +196,11 @@ class Native:
         t = Timing()
         self.check(self.lib.tsx_ctx_timing(h, C.byref(t)))
         return t
+
+    def ctx_records(self, h):
+        r = RecordsInfo()
+        self.check(self.lib.tsx_ctx_records(h, C.byref(r)))
+        return r
 
     def ctx_device(self, h):
         return self.check(self.lib.tsx_ctx_device(h))

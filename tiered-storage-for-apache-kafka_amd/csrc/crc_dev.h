@@ -25,6 +25,13 @@ __device__ static inline uint32_t crc_pow_pieces(const tsx_crc_tables* tab, uint
     return r;
 }
 
+// x^(8*m) mod P: the byte-granular sibling of crc_pow_pieces (a remainder moved over m bytes that are no multiple of a 16-byte piece:
+// the record-batch validator's spans begin and end at any byte, records_dev.h).  m < 2^36.
+__device__ static inline uint32_t crc_pow_bytes(const tsx_crc_tables* tab, uint64_t m) {
+    uint32_t t = 0x80000000u;
+    for (uint32_t i = 0; i < 8u * (uint32_t)(m & 15u); i++) t = crc_mulx(t);
+    return crc_mulmod(crc_pow_pieces(tab, (uint32_t)(m >> 4)), t);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // CRC32C of ONE buffer by ONE wave (java.util.zip.CRC32C semantics: init and xorout 0xFFFFFFFF).  Used where a wave already

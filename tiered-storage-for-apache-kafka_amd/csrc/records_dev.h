@@ -1,0 +1,199 @@
+// Record-batch validation (TSX_VALIDATE_RECORDS): what one wave does with the STREAM of a batch - its chunks, concatenated in descriptor
+// order - gfx950.  The stream is Kafka's log format v2: a sequence of record batches (DefaultRecordBatch.java: baseOffset @0, batchLength
+// @8, partitionLeaderEpoch @12, magic @16, crc @17, attributes @21 ..., all big-endian; the CRC32C covers [21, 12 + batchLength)).
+// Internal: not part of the C ABI.
+//
+// Every length in the stream is untrusted input.  The only way to a byte of the source is rec_seek(): it takes a stream position BELOW
+// the stream's length and yields the chunk that holds it, and every caller establishes `position < total` (or `end <= total`) before it
+// asks - a damaged length yields a verdict, never an address.
+#pragma once
+#include "crc_dev.h"
+
+#define TSX_REC_HEADER 61u              /* RECORD_BATCH_OVERHEAD: the smallest batch (no records) */
+#define TSX_REC_MIN_LEN 49              /* ... as its batchLength field says it (everything behind the first 12 bytes) */
+#define TSX_REC_SCAN_TILE 4096u         /* bytes of a chunk a walker without an entry examines per staging step */
+#define TSX_REC_SCAN_TRIES 8u           /* candidates a walker puts to the CRC before it gives up (the resolver then walks its chunk itself) */
+#define TSX_REC_SCAN_MAX_LEN (1u << 20) /* ... and the longest batch it puts to the CRC, unless its own chunk is longer: a candidate is a guess, and a guess
+                                           with a length of a GiB is a second of one wave's CRC (measured: 1.5 s per 1 GiB segment before this bound) */
+
+struct tsx_rec_view {                   // the stream, as the descriptors lay it out
+    const uint8_t* src;                 // the batch's source buffer (device addressable)
+    const uint64_t* pos;                // pos[k]: stream position of chunk k's first byte, pos[n] = the stream's length
+    const uint64_t* off;                // off[k]: chunk k's offset in src
+    uint32_t n;
+    uint64_t total;
+};
+
+struct tsx_rec_cursor { uint64_t lo, hi; const uint8_t* p; uint32_t ci; };     // chunk ci holds stream positions [lo, hi) at p
+
+__device__ static inline void rec_cursor_reset(tsx_rec_cursor& c) { c.lo = 0; c.hi = 0; c.p = nullptr; c.ci = 0; }
+
+// q < v.total.  Afterwards c.lo <= q < c.hi.  The next chunk first (a walk moves forward), else the last k with pos[k] <= q by bisection:
+// it is not empty, because pos[k + 1] > q.
+__device__ static inline void rec_seek(const tsx_rec_view& v, tsx_rec_cursor& c, uint64_t q) {
+    if (q >= c.lo && q < c.hi) return;
+    uint32_t k = c.ci + 1;
+    if (!(c.hi != 0 && k < v.n && v.pos[k] <= q && q < v.pos[k + 1])) {
+        uint32_t a = 0, b = v.n - 1;                                    // invariant: pos[a] <= q, answer in [a, b]
+        while (a < b) {
+            const uint32_t m = a + (b - a + 1) / 2;
+            if (v.pos[m] <= q) a = m; else b = m - 1;
+        }
+        k = a;
+    }
+    c.ci = k; c.lo = v.pos[k]; c.hi = v.pos[k + 1]; c.p = v.src + v.off[k];
+}
+
+__device__ static inline uint8_t rec_byte(const tsx_rec_view& v, tsx_rec_cursor& c, uint64_t q) {
+    rec_seek(v, c, q);
+    return c.p[q - c.lo];
+}
+
+__device__ static inline uint32_t rec_be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
+
+// CRC32C (java.util.zip.CRC32C) of stream positions [a, b), a <= b <= v.total, b - a < 2^32, by one wave; every lane calls and gets the
+// result.  cur: the wave's own (uniform) cursor - it stays where the span ended, so that a walk asks the tables (pinned memory: a read
+// crosses PCIe) once per chunk it enters and not once per batch.  The span is taken apart where it crosses from one chunk to the next; of
+// each part the bytes up to the first 16-byte aligned ADDRESS go to lane 63, the whole aligned pieces to the lanes in stripes of 64-byte
+// lines (crc32c_wave's way: slicing-by-4 over the tables in ldsTab), the rest to lane 62.  Every run starts from remainder 0 and is moved
+// to the span's end with crc_pow_bytes; the init word is the remainder 0xFFFFFFFF moved over the whole span.
+__device__ static inline uint32_t rec_crc(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, tsx_rec_cursor& cur, uint64_t a, uint64_t b,
+                                          const uint32_t* ldsTab, uint32_t lane) {
+    #define REC_CRC_W(x) { s ^= (x); s = ldsTab[3 * 256 + (s & 0xFF)] ^ ldsTab[2 * 256 + ((s >> 8) & 0xFF)] ^ ldsTab[256 + ((s >> 16) & 0xFF)] ^ ldsTab[s >> 24]; }
+    #define REC_CRC_B(x) { s ^= (x); for (int k_ = 0; k_ < 8; k_++) s = crc_mulx(s); }
+    uint32_t acc = 0;
+    for (uint64_t q = a; q < b;) {                                      // (uniform)
+        rec_seek(v, cur, q);
+        const uint64_t e = b < cur.hi ? b : cur.hi;
+        const uint8_t* const p = cur.p + (q - cur.lo);
+        const uint32_t L = (uint32_t)(e - q);
+        uint32_t head = (16u - (uint32_t)((uintptr_t)p & 15u)) & 15u;
+        if (head > L) head = L;
+        const uint32_t nq = (L - head) >> 4, tail = (L - head) & 15u;
+        const uint32_t per = (((nq + 63) >> 6) + 3) & ~3u;
+        const uint32_t p0 = min(lane * per, nq), p1 = min(p0 + per, nq);
+        const uint4* in = reinterpret_cast<const uint4*>(p + head);
+        uint32_t s = 0, i = p0;
+        for (; i + 4 <= p1; i += 4) {
+            const uint4 w0 = in[i], w1 = in[i + 1], w2 = in[i + 2], w3 = in[i + 3];
+            REC_CRC_W(w0.x) REC_CRC_W(w0.y) REC_CRC_W(w0.z) REC_CRC_W(w0.w)
+            REC_CRC_W(w1.x) REC_CRC_W(w1.y) REC_CRC_W(w1.z) REC_CRC_W(w1.w)
+            REC_CRC_W(w2.x) REC_CRC_W(w2.y) REC_CRC_W(w2.z) REC_CRC_W(w2.w)
+            REC_CRC_W(w3.x) REC_CRC_W(w3.y) REC_CRC_W(w3.z) REC_CRC_W(w3.w)
+        }
+        for (; i < p1; i++) {
+            const uint4 w = in[i];
+            REC_CRC_W(w.x) REC_CRC_W(w.y) REC_CRC_W(w.z) REC_CRC_W(w.w)
+        }
+        if (p1 > p0) acc ^= crc_mulmod(s, crc_pow_bytes(tab, (b - e) + tail + ((uint64_t)(nq - p1) << 4)));
+        if (lane == 63 && head) {
+            s = 0;
+            for (uint32_t k = 0; k < head; k++) REC_CRC_B(p[k])
+            acc ^= crc_mulmod(s, crc_pow_bytes(tab, (b - q) - head));
+        }
+        if (lane == 62 && tail) {
+            const uint8_t* t = p + head + ((size_t)nq << 4);
+            s = 0;
+            for (uint32_t k = 0; k < tail; k++) REC_CRC_B(t[k])
+            acc ^= crc_mulmod(s, crc_pow_bytes(tab, b - e));
+        }
+        q = e;
+    }
+    #undef REC_CRC_W
+    #undef REC_CRC_B
+    for (int o = 32; o; o >>= 1) acc ^= __shfl_xor(acc, o);
+    return ~(acc ^ crc_mulmod(0xFFFFFFFFu, crc_pow_bytes(tab, b - a)));
+}
+
+struct tsx_rec_lds {
+    uint32_t tab[4 * 256];                                              // slicing tables 0..3 of tsx_crc_tables
+    uint8_t hdr[64];                                                    // the header of the batch under examination
+    uint8_t tile[TSX_REC_SCAN_TILE + 64];                               // a walker without an entry: the bytes it looks for one in
+};
+
+__device__ static inline void rec_lds_init(const tsx_crc_tables* __restrict__ tab, tsx_rec_lds* L, uint32_t lane) {
+    const uint4* g = reinterpret_cast<const uint4*>(&tab->slice[0][0]);
+    uint4* l = reinterpret_cast<uint4*>(L->tab);
+    for (uint32_t i = lane; i < 4 * 256 / 4; i += 64) l[i] = g[i];
+    __syncthreads();
+}
+
+// The serial walk from `start` (a batch boundary, start <= stop <= total) over every batch that begins below `stop`; the whole wave
+// calls.  For each batch, in DefaultRecordBatch.ensureValid()'s order: at least a header left, batchLength >= 49 (signed), the batch
+// inside the stream, magic 2, CRC.  w->exit is where the first batch at or behind `stop` begins.  The next header's bytes are asked for
+// before the CRC of this batch runs: the load's latency passes under it.
+__device__ static inline void rec_walk(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, uint64_t start, uint64_t stop,
+                                       tsx_rec_lds* L, uint32_t lane, tsx_rec_walk* w) {
+    tsx_rec_cursor cur, ccur;                                           // the lanes' own (header bytes) and the wave's (CRC spans)
+    rec_cursor_reset(cur); rec_cursor_reset(ccur);
+    w->found = 1; w->entry = start; w->batches = 0; w->compressed = 0; w->bad_reason = 0; w->bad_pos = 0;
+    uint64_t pos = start;
+    bool have = false;
+    uint8_t nb = 0;
+    while (pos < stop) {
+        uint32_t why = 0;
+        if (v.total - pos < TSX_REC_HEADER) why = TSX_REC_TRUNCATED;
+        else {
+            if (!have && lane < TSX_REC_HEADER) nb = rec_byte(v, cur, pos + lane);
+            __syncthreads();                                            // (the last batch's readers of hdr are done)
+            if (lane < TSX_REC_HEADER) L->hdr[lane] = nb;
+            __syncthreads();
+            have = false;
+            const int32_t len = (int32_t)rec_be32(L->hdr + 8);
+            const uint64_t left = v.total - pos - 12;
+            if (len < TSX_REC_MIN_LEN) why = TSX_REC_LENGTH;
+            else if ((uint64_t)len > left) why = TSX_REC_TRUNCATED;
+            else if (L->hdr[16] != 2) why = TSX_REC_MAGIC;
+            else {
+                const uint32_t want = rec_be32(L->hdr + 17);
+                const uint32_t comp = (L->hdr[22] & 7u) != 0;
+                const uint64_t end = pos + 12 + (uint64_t)len;
+                if (end < stop && v.total - end >= TSX_REC_HEADER) { if (lane < TSX_REC_HEADER) nb = rec_byte(v, cur, end + lane); have = true; }
+                if (rec_crc(tab, v, ccur, pos + 21, end, L->tab, lane) != want) why = TSX_REC_CRC;
+                else { w->batches++; w->compressed += comp; pos = end; }
+            }
+        }
+        if (why) { w->bad_reason = why; w->bad_pos = pos; break; }
+    }
+    w->exit = pos;
+}
+
+// A walker that does not know where its chunk's first batch begins: from stream positions [lo, hi) the first one that looks like a header
+// (magic 2, a length that is at least a header's, stays inside the stream and is no longer than TSX_REC_SCAN_MAX_LEN or the chunk,
+// attribute bits 7..15 zero) AND whose CRC confirms.  Returns false when there is none among the first TSX_REC_SCAN_TRIES that look like
+// one: a chunk wholly inside a batch, a batch longer than the bound, or a hostile chunk - the resolver walks such a chunk itself.
+__device__ static inline bool rec_find_entry(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, uint64_t lo, uint64_t hi,
+                                             tsx_rec_lds* L, uint32_t lane, uint64_t* entry) {
+    tsx_rec_cursor cur, ccur;
+    rec_cursor_reset(cur); rec_cursor_reset(ccur);
+    uint32_t tries = 0;
+    const uint64_t max_len = hi - lo > TSX_REC_SCAN_MAX_LEN ? hi - lo : TSX_REC_SCAN_MAX_LEN;
+    for (uint64_t base = lo; base < hi; base += TSX_REC_SCAN_TILE) {
+        const uint64_t avail = v.total - base;
+        const uint32_t cnt = avail < TSX_REC_SCAN_TILE + 64 ? (uint32_t)avail : TSX_REC_SCAN_TILE + 64;
+        const uint32_t lim = hi - base < TSX_REC_SCAN_TILE ? (uint32_t)(hi - base) : TSX_REC_SCAN_TILE;
+        __syncthreads();
+        for (uint32_t i = lane; i < cnt; i += 64) L->tile[i] = rec_byte(v, cur, base + i);
+        __syncthreads();
+        for (uint32_t from = 0; from < lim;) {
+            uint32_t best = 0xFFFFFFFFu;
+            for (uint32_t i = (from & ~63u) + lane; i < lim && i + TSX_REC_HEADER <= cnt; i += 64) {
+                if (i < from) continue;
+                const uint8_t* h = L->tile + i;
+                if (h[16] != 2 || h[21] != 0 || (h[22] & 0x80)) continue;
+                const int32_t len = (int32_t)rec_be32(h + 8);
+                if (len < TSX_REC_MIN_LEN || (uint64_t)len > v.total - (base + i) - 12 || (uint64_t)len > max_len) continue;
+                best = i;
+                break;
+            }
+            for (int o = 32; o; o >>= 1) { const uint32_t x = __shfl_xor(best, o); best = x < best ? x : best; }
+            if (best == 0xFFFFFFFFu) break;
+            const uint64_t p = base + best;
+            const uint64_t end = p + 12 + (uint64_t)rec_be32(L->tile + best + 8);
+            if (rec_crc(tab, v, ccur, p + 21, end, L->tab, lane) == rec_be32(L->tile + best + 17)) { *entry = p; return true; }
+            if (++tries >= TSX_REC_SCAN_TRIES) return false;
+            from = best + 1;
+        }
+    }
+    return false;
+}

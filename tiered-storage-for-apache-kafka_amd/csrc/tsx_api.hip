@@ -88,6 +88,7 @@ extern "C" const char* tsx_strerror(int code) {
         case TSX_E_SHORT_CHUNK: return "encrypted chunk shorter than IV + tag";
         case TSX_E_UNSUPPORTED: return "unsupported parameter";
         case TSX_E_VERIFY: return "the frame written for this chunk does not restore it";
+        case TSX_E_RECORDS: return "invalid record batch in the source at or before this chunk";
         default: return "unknown error";
     }
 }
@@ -213,6 +214,7 @@ static void ctx_free_device_mem(tsx_ctx* c) {
     svc_free_host(c->dev, c->h_segflag);
     svc_free_host(c->dev, c->h_descs);
     svc_free_host(c->dev, c->h_verdicts);
+    svc_free_host(c->dev, c->h_records);
     if (c->h_keyraw) { memset(c->h_keyraw, 0, 128); svc_free_host(c->dev, c->h_keyraw); }
     if (c->h_key) { memset(c->h_key, 0, sizeof(tsx_gcm_key)); svc_free_host(c->dev, c->h_key); }
     for (auto& e : c->ev) if (e) hipEventDestroy(e);
@@ -361,6 +363,12 @@ extern "C" void tsx_ctx_destroy(tsx_ctx* c) {
 extern "C" int tsx_ctx_timing(const tsx_ctx* c, tsx_timing* out) {
     if (!c || !out) return TSX_E_INVAL;
     *out = c->timing;
+    return TSX_OK;
+}
+
+extern "C" int tsx_ctx_records(const tsx_ctx* c, tsx_records_info* out) {
+    if (!c || !out) return TSX_E_INVAL;
+    *out = c->records;
     return TSX_OK;
 }
 

@@ -541,6 +541,46 @@ static int gcm_verify_piece(tsx_run& r, const tsx_sub& sb, int32_t* gcode) {
 }
 // ======== end of verify on upload ======================================================================================================
 
+// ======== record-batch validation (TSX_VALIDATE_RECORDS) ================================================================================
+// The source of the whole batch - every piece's input has landed behind `staged` (nullptr: it was on the device to begin with) - as ONE
+// stream of Kafka record batches (records.hip): rcode[i] = 0 (no invalid batch begins in or before chunk i), TSX_E_RECORDS, or TSX_E_NOMEM
+// (never "not looked at").  Two ordinary kernels on the context's stream, next to whatever the batch's own stages are doing (a compressing
+// batch's waves have a second of work per chunk in front of them): the batch claims the reserved CUs like a fetch and waits with the
+// fetch side's safety net.  Everything the kernels say comes back through the context's pinned block.
+static int records_validate(tsx_run& r, hipEvent_t staged, int32_t* rcode) {
+    tsx_ctx* c = r.c;
+    for (uint32_t i = 0; i < r.n; i++) rcode[i] = TSX_E_NOMEM;
+    const size_t need = tsx_records_block_bytes(r.n);
+    if (c->records_cap < need) {
+        svc_free_host(c->dev, c->h_records); c->h_records = nullptr; c->hd_records = nullptr; c->records_cap = 0;
+        const size_t cap = need + need / 4 + 256;
+        if (hipHostMalloc((void**)&c->h_records, cap, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); c->h_records = nullptr; return TSX_OK; }
+        HIPCHK(hipHostGetDevicePointer((void**)&c->hd_records, c->h_records, 0));
+        c->records_cap = cap;
+    }
+    tsx_records_block_fill(c->h_records, r.descs, r.n);
+    svc_foreground_scope fg(c->dev);
+    if (staged) HIPCHK(hipStreamWaitEvent(c->st, staged, 0));
+    HIPCHK(hipEventRecord(c->ev[EV_RECORDS_BEGIN], c->st));
+    tsx_launch_records(c->st, c->dev->d_crc, r.d_src, c->hd_records, r.n);
+    HIPCHK(hipEventRecord(c->ev[EV_RECORDS_END], c->st));
+    HIPCHK(wait_event_watching(c, c->ev[EV_RECORDS_END]));
+    HIPCHK(hipGetLastError());
+    const tsx_rec_block b = tsx_records_block_at(c->h_records, r.n);
+    if (!__atomic_load_n(&b.head->done, __ATOMIC_ACQUIRE)) return TSX_OK;
+    for (uint32_t i = 0; i < r.n; i++) rcode[i] = b.verdicts[i];
+    tsx_records_info& o = c->records;
+    o.batches = b.head->batches; o.compressed_batches = b.head->compressed; o.first_bad_pos = b.head->first_bad_pos;
+    o.first_bad_reason = b.head->first_bad_reason; o.repaired_chunks = b.head->repaired;
+    o.ms = ev_ms(c->ev[EV_RECORDS_BEGIN], c->ev[EV_RECORDS_END]);
+    return TSX_OK;
+}
+// ... into chunks [lo, lo + n) of `descs`, before they reach the caller: a chunk that already carries another error keeps it
+static void records_merge(tsx_chunk_desc* descs, const int32_t* rcode, uint32_t lo, uint32_t n) {
+    for (uint32_t i = lo; i < lo + n; i++) if (rcode[i] && descs[i].status == TSX_OK) { descs[i].status = rcode[i]; descs[i].dst_len = 0; }
+}
+// ======== end of record-batch validation ===============================================================================================
+
 // ---- the compressing forward chain: members of the device's service ---------------------------------------------------------------------
 // Zero-copy output (round 4).  The wave that finishes a chunk writes its bytes straight into the caller's buffer over PCIe when the device
 // can address ALL of it (device_alias_of_range): posted writes of a few ms of a second-long wave, released to system scope before the
@@ -608,6 +648,8 @@ static int run_compress(tsx_run& r) {
     if (r.flags & TSX_VERIFY) vcode.assign(n, 0);
     std::vector<int32_t> gcode;                                         // TSX_VERIFY_GCM: the same of the GCM verifier
     if (r.flags & TSX_VERIFY_GCM) gcode.assign(n, 0);
+    std::vector<int32_t> rcode;                                         // TSX_VALIDATE_RECORDS: the same of the record-batch validator
+    if (r.flags & TSX_VALIDATE_RECORDS) rcode.assign(n, 0);
     // ---- the pieces ----
     std::vector<tsx_sub> subs;
     {
@@ -682,6 +724,9 @@ static int run_compress(tsx_run& r) {
         submitted = k + 1;
         if (rc) return abandon_all(rc);
     }
+    // ---- record-batch validation: every piece's input has landed (the last piece was published when its own had); the validator's two
+    // kernels run while the service compresses, and their verdicts are in hand before the first piece is handed back ----
+    if (!rcode.empty() && (rc = records_validate(r, r.host ? c->sub_ev[ns - 1][SUB_STAGED_IN] : nullptr, rcode.data()))) return abandon_all(rc);
     // ---- completions, in order; a piece's bytes travel back (or are packed down) while the later pieces still run ----
     size_t packed_at = 0; bool packed_full = false;
     const auto t_pub = std::chrono::steady_clock::now();
@@ -699,6 +744,7 @@ static int run_compress(tsx_run& r) {
         // move them (chunks the Zstandard verifier has just failed are skipped)
         if (r.enc && (rc = gcm_verify_piece(r, sb, gcode.data()))) return abandon_all(rc);
         if (!gcode.empty()) for (uint32_t i = sb.lo; i < sb.lo + sb.n; i++) if (gcode[i] && c->h_descs[i].status == TSX_OK) { c->h_descs[i].status = gcode[i]; c->h_descs[i].dst_len = 0; }
+        if (!rcode.empty()) records_merge(c->h_descs, rcode.data(), sb.lo, sb.n);
         memcpy(r.descs + sb.lo, c->h_descs + sb.lo, (size_t)sb.n * sizeof(tsx_chunk_desc));
         if (r.zc_dst) {
             // the bytes are where they belong; a packed batch is packed down in place.  (compress_zero_copy_ok: dst_size >= out_bytes, the
@@ -893,6 +939,8 @@ static int run_batch_inner(tsx_run& r) {
     };
     // The restored chunks of a fetch are what crosses PCIe (4 MiB each against 1.3 MB in): one copy stream moves them at ~31 GB/s - 8.7 of a
     // 64-chunk window's 10.4 ms; the pieces' copies alternate between two streams.
+    std::vector<int32_t> rcode;                                         // TSX_VALIDATE_RECORDS (transform only: run_batch clears the flag elsewhere)
+    if (r.flags & TSX_VALIDATE_RECORDS) rcode.assign(n, 0);
     bool out2 = inv_blocks && multi && r.host;
     if (out2 && !c->st_out2 && hipStreamCreateWithFlags(&c->st_out2, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); c->st_out2 = nullptr; out2 = false; }
     auto collect_piece = [&](size_t k) -> int {
@@ -904,14 +952,18 @@ static int run_batch_inner(tsx_run& r) {
         }
         HIPCHK(wait_event_watching(c, c->sub_ev[k][SUB_DONE]));              // descriptors of piece k are on the host
         memcpy(r.descs + sb.lo, c->h_descs + sb.lo, (size_t)sb.n * sizeof(tsx_chunk_desc));
+        if (!rcode.empty()) records_merge(r.descs, rcode.data(), sb.lo, sb.n);
         if (r.zc_dst) return TSX_OK;                                    // the bytes are in the caller's buffer already
         if (r.host && r.mode != 2) return copy_back(r, sb, &packed_at, &packed_full, (out2 && (k & 1)) ? c->st_out2 : c->st_out);
         return TSX_OK;
     };
-    if (multi) {
+    if (multi || !rcode.empty()) {
         for (size_t k = 0; k < ns; k++) if ((rc = enqueue_piece(k))) return rc;
+        // record-batch validation of a chain that does not compress: behind the last piece's input copy, and its verdicts are in hand
+        // before the first piece's descriptors reach the caller (the pieces are all queued first: no copy-out overlaps a later piece's kernels)
+        if (!rcode.empty() && (rc = records_validate(r, r.host ? c->sub_ev[ns - 1][SUB_STAGED_IN] : nullptr, rcode.data()))) return rc;
         for (size_t k = 0; k < ns; k++) if ((rc = collect_piece(k))) return rc;
-        for (size_t k = 1; k < ns; k++) HIPCHK(hipStreamWaitEvent(st, c->sub_ev[k][SUB_DONE], 0));   // the batch's end event covers every piece
+        if (multi) for (size_t k = 1; k < ns; k++) HIPCHK(hipStreamWaitEvent(st, c->sub_ev[k][SUB_DONE], 0));   // the batch's end event covers every piece
     } else {
         // software pipeline on the host: copy-in + kernels of piece k are queued before the host waits for piece k - 1's descriptors
         // (they say how many bytes each chunk produced) and queues its copy-out
@@ -971,18 +1023,20 @@ int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs,
     const bool packed = mem_kind == TSX_MEM_HOST_PACKED;
     if (packed && mode != 0) return TSX_E_INVAL;
     uint32_t flags = mode == 2 ? TSX_CRC : params->flags;
-    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC | TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM)) return TSX_E_INVAL;
+    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC | TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM | TSX_VALIDATE_RECORDS)) return TSX_E_INVAL;
     // the content checksum is the compressor's to write; a decoder verifies whatever frame declares one, asked or not.  Verify on upload
     // reads back what the compressor wrote: both modify TSX_COMPRESS on transform and mean nothing anywhere else
     if (mode == 0 && (flags & (TSX_ZSTD_CHECKSUM | TSX_VERIFY)) && !(flags & TSX_COMPRESS)) return TSX_E_INVAL;
     // ... and the GCM verifier reads back what the GCM stage wrote: a modifier of TSX_ENCRYPT on transform
     if (mode == 0 && (flags & TSX_VERIFY_GCM) && !(flags & TSX_ENCRYPT)) return TSX_E_INVAL;
-    if (mode != 0) flags &= ~(TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM);
+    // ... and the record-batch validator reads the source of an upload: a modifier of any transform
+    if (mode != 0) flags &= ~(TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM | TSX_VALIDATE_RECORDS);
     if (mode != 2) {
         if (params->aad_len > 64) return TSX_E_INVAL;
         if ((flags & TSX_COMPRESS) && !(params->zstd_level >= 0 && params->zstd_level <= 3)) return TSX_E_UNSUPPORTED;   // 0 = 3 (the library default), 1, 2, 3
         if ((flags & TSX_COMPRESS) && params->zstd_profile > TSX_ZSTD_PROFILE_1_5_7) return TSX_E_UNSUPPORTED;
     }
+    memset(&c->records, 0, sizeof c->records); c->records.first_bad_pos = ~0ull;
     if (n == 0) return TSX_OK;
     tsx_device_scope keep;
     if (hipSetDevice(c->dev->hip_id) != hipSuccess) return TSX_E_DEVICE;

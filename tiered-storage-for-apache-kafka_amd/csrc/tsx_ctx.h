@@ -13,6 +13,7 @@ enum {
     EV_H2D_FIRST,                       // on the copy-in stream, in front of the first piece's input copy
     EV_D2H_LAST,                        // on the copy-out stream, behind the last piece's output copies
     EV_VERIFY_BEGIN, EV_VERIFY_END,     // on st: one slice (or one phase-two chunk) of verify on upload, in the middle of a compressing batch
+    EV_RECORDS_BEGIN, EV_RECORDS_END,   // on st: the record-batch validator's two kernels (tsx_records_info.ms)
     EV_COUNT
 };
 // tsx_ctx::sub_ev[k][]: the events of piece k
@@ -67,6 +68,10 @@ struct tsx_ctx {
     bool key_staged = false;                       // a fused compressing batch's GCM verifier has brought the key schedule to d_key (wiped behind every piece)
     // verify on upload (TSX_VERIFY, and TSX_VERIFY_GCM of a compressing batch): the verifier's words per chunk of a slice, pinned, and as the device addresses them (created by the first verifying batch)
     uint32_t* h_verdicts = nullptr; uint32_t* hd_verdicts = nullptr; size_t verdicts_cap = 0;
+    // record-batch validation (TSX_VALIDATE_RECORDS): the validator's block (tsx_internal.h: tsx_rec_block), pinned, and as the device addresses it
+    // (created by the first validating batch); what the last batch found
+    uint8_t* h_records = nullptr; uint8_t* hd_records = nullptr; size_t records_cap = 0;
+    tsx_records_info records{};
     uint32_t verify_block_form = 0, verify_fallback = 0;   // chunks of the last batch the block form judged / that were decoded in full (test hook)
 };
 

@@ -208,3 +208,33 @@ void tsx_launch_gcm(hipStream_t st, const tsx_aes_tables* d_aes, const tsx_gcm_k
 void tsx_launch_gcm_verify(hipStream_t st, const tsx_aes_tables* d_aes, const tsx_gcm_key* d_key, const tsx_gcm_chunk* d_chunks,
                            const tsx_chunk_desc* descs, uint32_t n, uint32_t max_len, const uint8_t* ref, const uint8_t* delivered,
                            uint32_t* d_partials, uint32_t* verdicts, int32_t* d_status);
+
+// ---------------------------------------------------------------------------------------------------
+// Record-batch validation (TSX_VALIDATE_RECORDS; records.hip, records_dev.h)
+// ---------------------------------------------------------------------------------------------------
+// tsx_records_info.first_bad_reason
+#define TSX_REC_TRUNCATED 1u   /* fewer than 61 bytes left, or the batch reaches beyond the stream's end */
+#define TSX_REC_LENGTH    2u   /* batchLength < 49 (as a signed value) */
+#define TSX_REC_MAGIC     3u
+#define TSX_REC_CRC       4u
+
+struct tsx_rec_walk {            // what one walker (or the resolver in its place) has to say about the batches that begin in its chunk
+    uint64_t entry, exit;        // where its first batch begins / where the first batch at or behind the next chunk's first byte begins
+    uint64_t bad_pos;            // bad_reason != 0: the first invalid batch (the walk ended there)
+    uint32_t found;              // 0: no entry (the chunk lies inside one batch, or is empty)
+    uint32_t batches, compressed, bad_reason;
+};
+struct tsx_rec_head {            // the resolver's result
+    uint64_t batches, compressed, first_bad_pos;
+    uint32_t first_bad_reason, repaired, done, pad_[7];
+};
+// One block of PINNED memory per validating batch holds everything the two kernels read and write besides the source bytes - the
+// resolver's result, the chunks' stream positions and source offsets, the walkers' results, the per-chunk verdicts: nothing small is copied
+// (a blit kernel waits behind a chip full of compressor waves), and the walkers' 40 bytes per chunk cross PCIe once each way.
+struct tsx_rec_block { tsx_rec_head* head; uint64_t* pos; uint64_t* off; tsx_rec_walk* walks; int32_t* verdicts; };
+size_t tsx_records_block_bytes(uint32_t n);
+tsx_rec_block tsx_records_block_at(void* base, uint32_t n);
+// Host: lays the block out for descs[0 .. n) - positions, offsets, every verdict "not looked at" (TSX_E_NOMEM), head cleared.
+void tsx_records_block_fill(void* h_base, const tsx_chunk_desc* descs, uint32_t n);
+// records_walk_kernel (one wave per chunk) and records_resolve_kernel (one wave) on st; hd_base: the block as the device addresses it.
+void tsx_launch_records(hipStream_t st, const tsx_crc_tables* d_tab, const uint8_t* src, void* hd_base, uint32_t n);

@@ -456,9 +456,10 @@ Bytes BaseTransformChunkEnumeration::nextElement() {
 
 GpuTransformChunkEnumeration::GpuTransformChunkEnumeration(std::shared_ptr<Backend> be, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                                            std::optional<DataKeyAndAAD> enc, IvSupplier iv, int batchChunks, bool withCrc, uint32_t profile, bool readAhead,
-                                                           int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify)
+                                                           int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify, bool recordsValidate)
     : be_(std::move(be)), inner_(std::move(inner)), compress_(compress), enc_(std::move(enc)), iv_(std::move(iv)), batch_(batchChunks), withCrc_(withCrc),
-      profile_(profile), readAhead_(readAhead), level_(zstdLevel), checksum_(zstdChecksum), verify_(zstdVerify), gcmVerify_(gcmVerify) {
+      profile_(profile), readAhead_(readAhead), level_(zstdLevel), checksum_(zstdChecksum), verify_(zstdVerify), gcmVerify_(gcmVerify),
+      recordsValidate_(recordsValidate) {
     if (!inner_) throw std::invalid_argument("inner cannot be null");
     if (level_ < 0 || level_ > 3) throw std::invalid_argument("zstd level must be 1, 2 or 3 (0 = library default), " + std::to_string(level_) + " given");
     if (checksum_ && !compress_) throw std::invalid_argument("zstd checksum needs compression");
@@ -480,8 +481,12 @@ GpuTransformChunkEnumeration::Batch GpuTransformChunkEnumeration::transformNextB
     std::vector<Bytes> in;
     while ((int)in.size() < batch_ && inner_->hasMoreElements()) in.push_back(inner_->nextElement());
     if (in.empty()) return out;
-    const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u);
-    if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !withCrc_) { out.chunks = std::move(in); return out; }     // pure base: nothing to do
+    if (recordsValidate_ && inner_->hasMoreElements())
+        throw std::logic_error("segment.records.validate: the whole segment must fit one batch (batchChunks x chunk size = " + std::to_string(batch_) + " x " +
+                               std::to_string(inner_->originalChunkSize()) + " bytes); it is not validated in part");
+    const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u) |
+                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u);
+    if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !withCrc_ && !recordsValidate_) { out.chunks = std::move(in); return out; }     // pure base: nothing to do
     std::vector<tsx_chunk_desc> d(in.size());
     size_t so = 0, dofs = 0;
     for (size_t i = 0; i < in.size(); i++) {
@@ -518,8 +523,12 @@ GpuTransformChunkEnumeration::PackedBatch GpuTransformChunkEnumeration::transfor
     std::vector<Bytes> in;
     while ((int)in.size() < batch_ && inner_->hasMoreElements()) in.push_back(inner_->nextElement());
     if (in.empty()) return out;
-    const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u);
-    if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0) {                   // pure base: the chunks are the object
+    if (recordsValidate_ && inner_->hasMoreElements())
+        throw std::logic_error("segment.records.validate: the whole segment must fit one batch (batchChunks x chunk size = " + std::to_string(batch_) + " x " +
+                               std::to_string(inner_->originalChunkSize()) + " bytes); it is not validated in part");
+    const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u) |
+                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u);
+    if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !recordsValidate_) {      // pure base: the chunks are the object
         for (const Bytes& c : in) {
             out.object.insert(out.object.end(), c.begin(), c.end());
             out.sizes.push_back((int)c.size());

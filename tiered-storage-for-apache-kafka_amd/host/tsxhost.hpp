@@ -247,7 +247,8 @@ public:
     GpuTransformChunkEnumeration(std::shared_ptr<Backend> backend, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                  std::optional<DataKeyAndAAD> encryption, IvSupplier ivSupplier = secureRandomIvSupplier(),
                                  int batchChunks = 64, bool withCrc = false, uint32_t zstdProfile = TSX_ZSTD_PROFILE_1_5_7, bool readAhead = true,
-                                 int zstdLevel = 0, bool zstdChecksum = false, bool zstdVerify = false, bool gcmVerify = false);
+                                 int zstdLevel = 0, bool zstdChecksum = false, bool zstdVerify = false, bool gcmVerify = false,
+                                 bool recordsValidate = false);
     ~GpuTransformChunkEnumeration() override;
     // Zstandard level of the frames (compression.zstd.level): 0 = the library default (3, what the reference uses), 1, 2 or 3;
     // anything else is refused here, not at the first batch
@@ -263,6 +264,11 @@ public:
     // and authenticated on the device, against the bytes that went into the stage, before the chunk is handed on; a chunk that fails
     // (TSX_E_VERIFY) raises what any failed chunk raises.  Refused here when the chain does not encrypt.
     bool gcmVerify() const { return gcmVerify_; }
+    // validate the source (segment.records.validate, TSX_VALIDATE_RECORDS): the segment's bytes, as ONE stream, are walked on the device as a
+    // Kafka v2 log before anything is handed on; the chunk in which the first invalid record batch begins and every chunk behind it fail
+    // (TSX_E_RECORDS, raised like any failed chunk).  The whole segment must fit ONE batch (batchChunks x chunk size): a first batch that
+    // does not exhaust `inner` is refused with std::logic_error, never validated in part.
+    bool recordsValidate() const { return recordsValidate_; }
     int originalChunkSize() const override { return inner_->originalChunkSize(); }
     std::optional<int> transformedChunkSize() const override { return transformedChunkSize_; }
     bool hasMoreElements() override;
@@ -295,6 +301,7 @@ private:
     bool checksum_;
     bool verify_;
     bool gcmVerify_;
+    bool recordsValidate_;
     std::optional<int> transformedChunkSize_;
     std::vector<Bytes> ready_;
     size_t next_ = 0;
@@ -346,6 +353,7 @@ public:
     bool zstdChecksum() const { return inner_->zstdChecksum(); }
     bool zstdVerify() const { return inner_->zstdVerify(); }
     bool gcmVerify() const { return inner_->gcmVerify(); }
+    bool recordsValidate() const { return inner_->recordsValidate(); }
 
 private:
     bool nextBatch();

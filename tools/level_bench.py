@@ -11,8 +11,14 @@ rows of the verifying runs carry the verifier's own time of the last batch (tsx_
 --verify-gcm: the same for the GCM stage's verify on upload (TSX_VERIFY_GCM): off on, on off in one process; the verifying runs' rows carry
 the GCM stage's time and launches of the last batch (tsx_timing.gcm_ms, gcm_launches: the verifier's, the waves encrypt their own frames).
 The rows are appended to --out as well (default with --verify-gcm: profiles/gcm_verify_level_bench.jsonl).
+--records: record-batch validation (TSX_VALIDATE_RECORDS) off / on / on / off in one process, on ONE segment of content B that is a valid
+stream from its first byte to its last (64 distinct B chunks, each cut at its last complete batch, repeated up to 256 chunks of 4 MiB:
+batches cross chunk boundaries wherever they fall), level 3, --callers contexts.  The validating runs' rows carry the validator's own time
+and counters of the last 256-chunk batch (tsx_records_info.ms, repaired_chunks, batches) and, next to them, the separate-stage CRC
+kernels' crc_ms over the same bytes (tsx_crc32c_batch): what streaming those bytes through a CRC costs.  Default --out:
+profiles/records_level_bench.jsonl.
   python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8] [--levels 3] [--checksum] [--verify]
-                              [--verify-gcm] [--out FILE]"""
+                              [--verify-gcm] [--records] [--out FILE]"""
 import argparse
 import ctypes
 import json
@@ -34,6 +40,79 @@ def _gen_b_chunk(a):
     return synth.gen_chunk("B", a[0], a[1], a[2], a[3])
 
 
+def _gen_b_stream_piece(a):
+    """(worker of a spawned process pool) one chunk of content B cut at the end of its last complete batch."""
+    from tsxform import synth
+    c = synth.gen_chunk("B", a[0], a[1], a[2], a[3])
+    p, l = synth.record_batches_of(c)[-1]
+    return c[:p + l]
+
+
+def records_bench(args, emit):
+    import torch  # before libtsxform: one shared HIP runtime
+    import tsxform
+    from tsxform import synth
+    import multiprocessing as mp
+    from concurrent.futures import ProcessPoolExecutor
+    nat = tsxform._native
+    N = tsxform.get()
+    dev = torch.device("cuda", 0)
+    CH, T = synth.CHUNK, args.callers
+    t_gen = time.perf_counter()
+    with ProcessPoolExecutor(16, mp_context=mp.get_context("spawn")) as ex:
+        pieces = list(ex.map(_gen_b_stream_piece, [(1000, 0, c, CH) for c in range(64)]))
+    stream = np.concatenate([pieces[i % 64] for i in range(256)])
+    total = int(stream.size)
+    n = (total + CH - 1) // CH
+    gen_s = time.perf_counter() - t_gen
+    flags = nat.COMPRESS | nat.ENCRYPT | nat.CRC
+    slot = (N.transformed_bound(CH, flags) + 63) // 64 * 64
+    src = torch.from_numpy(stream).to(dev)
+    dsts = [torch.empty(n * slot, dtype=torch.uint8, device=dev) for _ in range(T)]
+    d = np.zeros(n, nat.DESC_DTYPE)
+    d["src_off"] = np.arange(n, dtype=np.uint64) * CH; d["src_len"] = CH; d["src_len"][n - 1] = total - (n - 1) * CH
+    d["dst_off"] = np.arange(n, dtype=np.uint64) * slot; d["dst_cap"] = slot
+    for i in range(n):
+        d["iv"][i] = np.frombuffer(synth.iv_for(0, i), np.uint8)
+    ctxs = [N.ctx_create(0, n, CH) for _ in range(T)]
+    dc = d.copy()
+    N.crc32c_batch(dc, src.data_ptr(), nat.MEM_DEVICE, ctx=ctxs[0], src_size=total)
+    N.crc32c_batch(dc, src.data_ptr(), nat.MEM_DEVICE, ctx=ctxs[0], src_size=total)
+    crc_ms = N.ctx_timing(ctxs[0]).crc_ms
+    rows = []
+    for on in (False, True, True, False):
+        p = nat.Native.make_params(flags | (nat.VALIDATE_RECORDS if on else 0), synth.KEY, synth.AAD, zstd_level=3)
+        ds = [d.copy() for _ in range(T)]
+
+        def step(t):
+            N.transform_batch(p, ds[t], src.data_ptr(), dsts[t].data_ptr(), dsts[t].numel(), nat.MEM_DEVICE, ctx=ctxs[t], src_size=total)
+        for w in range(max(args.warmup, 1)):
+            for t in (range(T) if w == 0 else range(1)):
+                step(t)
+        torch.cuda.synchronize()
+        N.service_quiesce(0)
+
+        def worker(t):
+            for _ in range(t, args.steps, T):
+                step(t)
+        t0 = time.perf_counter()
+        th = [threading.Thread(target=worker, args=(t,)) for t in range(T)]
+        [x.start() for x in th]
+        [x.join() for x in th]
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        N.service_quiesce(0)
+        ok = all(bool((x["status"] == 0).all()) for x in ds) and all(bool((x["dst_len"] == ds[0]["dst_len"]).all()) for x in ds)
+        r = N.ctx_records(ctxs[0])
+        row = {"content": "B stream", "level": 3, "records": on, "gibs": round(args.steps * total / GiB / el, 3), "elapsed_s": round(el, 3), "chunks": n, "stream_bytes": total,
+               "steps": args.steps, "callers": T, "all_ok": bool(ok), "records_ms": round(r.ms, 3), "repaired_chunks": r.repaired_chunks, "batches": r.batches,
+               "first_bad_pos": None if r.first_bad_pos == 0xFFFFFFFFFFFFFFFF else r.first_bad_pos, "crc_ms": round(crc_ms, 3), "generated_in_s": round(gen_s, 1)}
+        rows.append(row)
+        emit(row)
+    emit({"metric": "GiB/s of original bytes, record-batch validation off / on / on / off", "runs": [r["gibs"] for r in rows],
+          "records_ms": [r["records_ms"] for r in rows if r["records"]], "crc_ms": crc_ms, "all_ok": all(r["all_ok"] for r in rows), "tsxform": N.version()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -47,8 +126,11 @@ def main():
     ap.add_argument("--checksum", action="store_true", help="each level with and without TSX_ZSTD_CHECKSUM, alternating")
     ap.add_argument("--verify", action="store_true", help="each level without and with TSX_VERIFY, alternating")
     ap.add_argument("--verify-gcm", action="store_true", help="each level without and with TSX_VERIFY_GCM, alternating")
+    ap.add_argument("--records", action="store_true", help="TSX_VALIDATE_RECORDS off / on / on / off on one valid segment of content B")
     ap.add_argument("--out", default=None, help="append every JSON line to this file as well")
     args = ap.parse_args()
+    if args.records and not args.out:
+        args.out = os.path.join(ROOT, "profiles", "records_level_bench.jsonl")
     if args.verify_gcm and not args.out:
         args.out = os.path.join(ROOT, "profiles", "gcm_verify_level_bench.jsonl")
 
@@ -59,6 +141,8 @@ def main():
             with open(args.out, "a") as f:
                 f.write(line + "\n")
 
+    if args.records:
+        return records_bench(args, emit)
     import torch  # before libtsxform: one shared HIP runtime
     import tsxform
     from oracle import oracle as o
