@@ -201,6 +201,11 @@ def test_zstd_decoder_errors(gpu, oracle):
     no_size = b"\x28\xb5\x2f\xfd\x00\x58" + b"\x01\x00\x00"
     outs, d = pc.run_detransform(gpu, nat.COMPRESS, [good, b"\x00" + good[1:], good[:len(good) // 2], no_size, good], [70000, 70000, 70000, 16, 100])
     assert list(d["status"]) == [0, nat.E_BAD_FRAME, nat.E_BAD_FRAME, nat.E_BAD_SIZE, nat.E_DST_TOO_SMALL] and outs[0] == K.tobytes()
+    # two damaged bytes in the middle: libzstd's verdict on the frame decides (tests/frame_vocab_cases.py, apply_rules)
+    from tests import frame_vocab_cases as fv
+    corrupt = bytearray(good); corrupt[len(good) // 2] ^= 0xFF; corrupt[len(good) // 2 + 1] ^= 0x55
+    outs, d = pc.run_detransform(gpu, nat.COMPRESS, [bytes(corrupt)], [70000])
+    fv.check_against_libzstd(oracle, [bytes(corrupt)], [70000], d["status"], outs)
 
 
 def test_quarter_gib_full_chain_device_resident(gpu, oracle):
@@ -242,6 +247,8 @@ def test_zstd_decoder_survives_corrupt_frames(gpu, oracle):
     outs, d = pc.run_detransform(gpu, nat.COMPRESS, blobs, sizes)
     assert set(int(x) for x in d["status"]) <= {0, nat.E_BAD_FRAME, nat.E_BAD_SIZE, nat.E_DST_TOO_SMALL}
     assert (d["status"] != 0).sum() >= 200
+    from tests import frame_vocab_cases as fv
+    fv.check_against_libzstd(oracle, blobs, sizes, d["status"], outs)      # rejected where libzstd rejects, libzstd's bytes where it restores any
     good = oracle.zstd_compress_chunk(np.arange(5000, dtype=np.uint8).tobytes())       # the device still works afterwards
     outs, d = pc.run_detransform(gpu, nat.COMPRESS, [good], [5000])
     assert d["status"][0] == 0 and outs[0] == np.arange(5000, dtype=np.uint8).tobytes()

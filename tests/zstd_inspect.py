@@ -137,6 +137,13 @@ class Block:
     tables: dict = field(default_factory=dict)    # 'll'/'of'/'ml' -> (norm, al) for compressed mode
     seqs: list = field(default_factory=list)      # (ll, ml, offBase)
     literals: bytes = b""
+    # layout of a compressed block, offsets from the block's first byte (tests/frame_vocab_cases.py cuts frames into regions with them)
+    lit_format: int = 0        # Size_Format of the literals section header
+    lit_hl: int = 0            # bytes of the literals section header
+    huf_tree_size: int = 0     # bytes of the Huffman tree description (0: treeless, raw, RLE)
+    seq_at: int = 0            # where the sequences section starts
+    seq_tables_at: int = 0     # behind the sequence count and the modes byte: the first table description
+    seq_stream_at: int = 0     # behind the table descriptions: the sequence bitstream
 
 
 class FrameState:
@@ -232,7 +239,7 @@ def _parse_compressed_block(data, blk, st: FrameState, decode=True):
             regen = (b0 >> 4) + (data[1] << 4); hl = 2
         else:
             regen = (b0 >> 4) + (data[1] << 4) + (data[2] << 12); hl = 3
-        blk.lit_regen = regen
+        blk.lit_regen = regen; blk.lit_format, blk.lit_hl = sf, hl
         if lt == 0:
             blk.literals = bytes(data[hl:hl + regen]); p = hl + regen
         else:
@@ -250,6 +257,7 @@ def _parse_compressed_block(data, blk, st: FrameState, decode=True):
         regen = (v >> 4) & ((1 << bits) - 1)
         csize = v >> (4 + bits)
         blk.lit_regen, blk.lit_csize, blk.lit_streams = regen, csize, streams
+        blk.lit_format, blk.lit_hl = sf, hl
         q = hl
         if lt == 2:
             w, used, kind = _read_huf_weights(data, q)
@@ -257,6 +265,7 @@ def _parse_compressed_block(data, blk, st: FrameState, decode=True):
             table, mb, wfull = _huf_dtable(w)
             blk.huf_weights = wfull
             st.huf = (table, mb)
+            blk.huf_tree_size = used
             q += used
         elif st.huf is None:
             raise ValueError("treeless literals without a previous table")
@@ -273,6 +282,7 @@ def _parse_compressed_block(data, blk, st: FrameState, decode=True):
                 blk.literals = b"".join(_huf_decode_stream(pp, table, mb, c) for pp, c in zip(parts, counts))
         p = hl + csize
     # sequences section
+    blk.seq_at = blk.seq_tables_at = blk.seq_stream_at = p
     b = data[p]
     if b == 0:
         nbseq = 0; p += 1
@@ -283,11 +293,13 @@ def _parse_compressed_block(data, blk, st: FrameState, decode=True):
     else:
         nbseq = data[p + 1] + (data[p + 2] << 8) + 0x7F00; p += 3
     blk.nbseq = nbseq
+    blk.seq_tables_at = blk.seq_stream_at = p
     if nbseq == 0:
         if p != len(data):
             raise ValueError("trailing bytes after empty sequence section")
         return
     modes = data[p]; p += 1
+    blk.seq_tables_at = p
     m = ((modes >> 6) & 3, (modes >> 4) & 3, (modes >> 2) & 3)
     blk.modes = tuple(["predefined", "rle", "compressed", "repeat"][x] for x in m)
     tabs = {}
@@ -305,6 +317,7 @@ def _parse_compressed_block(data, blk, st: FrameState, decode=True):
                 raise ValueError("repeat mode without previous table")
             tabs[name] = st.fse[name]
         st.fse[name] = tabs[name]
+    blk.seq_stream_at = p
     if not decode:
         return
     bb = BackBits(data[p:])
