@@ -166,6 +166,27 @@ def test_an_offset_behind_the_chunk_and_a_chunk_that_failed_before_are_left_alon
     assert [dst[doff[i]:doff[i] + int(d["dst_len"][i])].tobytes() for i in (0, 2)] == [base[0], base[2]]
 
 
+def test_no_memory_for_the_verifier_is_said_per_chunk(emu):
+    """The one allocation of a compressing batch's GCM verifier - its pinned verdict words - fails: no chunk has been examined, so none is
+    TSX_OK.  (An encrypt-only batch verifies in stream and allocates nothing.)"""
+    emu.lib.hipemu_fail_alloc_at.argtypes = [ctypes.c_long]; emu.lib.hipemu_alloc_calls.restype = ctypes.c_long
+    chunks = [synth.gen_chunk("K", 57, 0, 0, 30000), synth.gen_chunk("R", 57, 0, 1, 15000), np.zeros(0, np.uint8)]
+    h = emu.ctx_create(0, 0, 0)
+    try:
+        want, d0 = gv.run_transform(emu, gv.CE, chunks, "host", ctx=h)  # (the context has its workspace: the verifier's words are the one allocation left)
+        assert (d0["status"] == 0).all()
+        emu.lib.hipemu_fail_alloc_at(1)
+        try:
+            outs, d = gv.run_transform(emu, gv.CE | gv.VG, chunks, "host", ctx=h)
+            reached = emu.lib.hipemu_alloc_calls()
+        finally:
+            emu.lib.hipemu_fail_alloc_at(0)
+        assert reached >= 1 and (d["status"] == nat.E_NOMEM).all() and (d["dst_len"] == 0).all() and outs == [b""] * 3
+        gv.check_clean(emu, gv.CE, chunks, "host", ctx=h, want=want)
+    finally:
+        emu.ctx_destroy(h)
+
+
 def test_the_key_schedule_does_not_stay_on_the_device(emu, ctx):
     residue = emu.lib.tsx_debug_key_residue; residue.restype = ctypes.c_int; residue.argtypes = [ctypes.c_void_p]
     chunks = gv.damage_comp_chunks()

@@ -157,6 +157,29 @@ def test_a_chunk_that_carries_another_error_keeps_it(emu, ctx, segment):
     assert [int(x) for x in d["status"]] == want and (d["dst_len"][k:] == 0).all()
 
 
+@pytest.mark.parametrize("mem,cfg", [("zero_copy", {}), ("host", {}), ("packed", {}), ("host", {"stages_separate": 1})])
+def test_a_chunk_that_a_verifier_and_the_validator_fail_reports_the_verifier(emu, ctx, segment, mem, cfg):
+    """All three checks on one compressing batch whose second record batch is damaged: the order in which their verdicts reach a chunk is
+    what the caller sees as precedence - the Zstandard verifier, the GCM verifier, then the validator.  A chunk behind the bad record
+    batch that a verifier fails as well is TSX_E_VERIFY, in front of it only the verifiers speak."""
+    small = segment[:rc.batches_of(segment)[3][0]]
+    bad = rc.flip(small, rc.batches_of(small)[1][0] + 19)
+    sizes = rc.cut(bad, -(-len(bad) // 16))
+    assert len(sizes) == 16 and sizes[0] == 3298
+    k = rc.expected_statuses(sizes, rc.reference_walk(bad)[2]).index(rc.E_RECORDS)
+    assert k == 3
+    flags = CE | nat.CRC
+    want, d0 = rc.run(emu, flags, bad, sizes, mem, ctx, **cfg)
+    assert (d0["status"] == 0).all()
+    V, R = gv.E_VERIFY, rc.E_RECORDS
+    for src_hit, out_hit, exp in ((k - 1, k + 1, [0, 0, V, R, V] + [R] * 11), (k + 2, k - 1, [0, 0, V, R, R, V] + [R] * 10)):
+        outs, d = rc.run(emu, flags | nat.VERIFY | nat.VERIFY_GCM | rc.VR, bad, sizes, mem, ctx, verify_damage_src_chunk=src_hit, verify_damage_src_off=100,
+                         verify_damage_out_chunk=out_hit, verify_damage_out_off=20, **cfg)
+        assert (V, R) == (-10, -11) and [int(x) for x in d["status"]] == exp, (mem, cfg, src_hit, out_hit, [int(x) for x in d["status"]])
+        assert (d["dst_len"][2:] == 0).all() and outs[2:] == [b""] * 14, (mem, cfg, src_hit)
+        assert outs[:2] == want[:2] and [int(x) for x in d["dst_len"][:2]] == [len(w) for w in want[:2]], (mem, cfg, src_hit)
+
+
 # ---- 5. speculation has to lose and still be right ---------------------------------------------------------------------------
 def test_a_valid_batch_inside_a_record_value_is_not_counted(emu, ctx):
     s = rc.nested_stream()

@@ -10,6 +10,7 @@ import pytest
 
 import tsxform
 from tests import checksum_cases as cc
+from tests import gcm_verify_cases as gv
 from tests import parity_cases as pc
 from tests import verify_cases as vc
 from tsxform import synth
@@ -119,3 +120,45 @@ def test_a_chunk_handed_back_and_restarted_verifies_clean(emu, oracle):
         finally:
             emu.lib.hipemu_relocate_after(0); emu.lib.hipemu_cu_key_shift(0)
     assert s1["returned_chunks"] - s0["returned_chunks"] >= 1, (s0, s1)
+
+
+# ---- 6. no memory ----------------------------------------------------------------------------------------------------------
+def _armed(emu, k, run):
+    """run() with the k-th allocation from here on failing once.  -> run()'s result, once that allocation has been reached."""
+    emu.lib.hipemu_fail_alloc_at.argtypes = [ctypes.c_long]; emu.lib.hipemu_alloc_calls.restype = ctypes.c_long
+    emu.lib.hipemu_fail_alloc_at(k)
+    try:
+        res = run()
+        reached = emu.lib.hipemu_alloc_calls()
+    finally:
+        emu.lib.hipemu_fail_alloc_at(0)
+    assert reached >= k, (k, reached)
+    return res
+
+
+@pytest.mark.parametrize("k,n,fallback", [(1, 30000, False), (2, 540000, False), (3, 680000, True)])
+def test_no_memory_for_the_verifier_is_said_per_chunk(emu, k, n, fallback):
+    """Each allocation of a verifying call fails once, on a context that has its own workspace: 1 = the context's pinned verdict words,
+    2 = the device's workspace (no chunk of the piece has been examined: every one is TSX_E_NOMEM), 3 = the buffer a chunk is restored
+    into in phase two (that chunk alone).  The verifier's workspace and its phase-two buffer belong to the device and outlive every test:
+    for their allocation to be reached they must have to GROW, so the batch is larger, in chunks (the empty ones cost nothing) and in
+    bytes (n incompressible ones: the emulated compressor is through them at once), than any verifying piece before it - 400000 bytes
+    in 40 chunks (tests/verify_cases.py), and n is 140000 more each time.  In phase two the first chunk, larger than any before it, is the one that needs a new buffer.
+    Host memory, in one piece: the caller allocates nothing between arming and the call."""
+    chunks = [synth.gen_chunk("R", 57, 0, 1, n), synth.gen_chunk("K", 57, 0, 0, 30000)] + [np.zeros(0, np.uint8)] * (1 if k == 1 else 46)
+    flags = nat.COMPRESS | nat.ENCRYPT
+    one = {"no_pipeline": 1}
+    cfg = dict(one, verify_force_fallback=1) if fallback else one
+    h = emu.ctx_create(0, 0, 0)
+    try:
+        want, d0 = gv.run_transform(emu, flags, chunks, "host", ctx=h, **one)
+        assert (d0["status"] == 0).all()
+        outs, d = _armed(emu, k, lambda: gv.run_transform(emu, flags | nat.VERIFY, chunks, "host", ctx=h, **cfg))
+        failed = [0] if fallback else range(len(chunks))
+        assert [int(x) for x in d["status"]] == [nat.E_NOMEM if i in failed else 0 for i in range(len(chunks))]
+        for i in range(len(chunks)):
+            assert (outs[i] == b"" and d["dst_len"][i] == 0) if i in failed else outs[i] == want[i], i
+        outs, d = gv.run_transform(emu, flags | nat.VERIFY, chunks, "host", ctx=h, **cfg)
+        assert (d["status"] == 0).all() and outs == want
+    finally:
+        emu.ctx_destroy(h)

@@ -63,6 +63,11 @@ def test_a_chunk_that_carries_another_error_keeps_it(gpu, ctx, segment):
     emu_tests.test_a_chunk_that_carries_another_error_keeps_it(gpu, ctx, segment)
 
 
+@pytest.mark.parametrize("mem,cfg", [("zero_copy", {}), ("host", {}), ("packed", {}), ("host", {"stages_separate": 1})])
+def test_a_chunk_that_a_verifier_and_the_validator_fail_reports_the_verifier(gpu, ctx, segment, mem, cfg):
+    emu_tests.test_a_chunk_that_a_verifier_and_the_validator_fail_reports_the_verifier(gpu, ctx, segment, mem, cfg)
+
+
 def test_a_valid_batch_inside_a_record_value_is_not_counted(gpu, ctx):
     emu_tests.test_a_valid_batch_inside_a_record_value_is_not_counted(gpu, ctx)
 

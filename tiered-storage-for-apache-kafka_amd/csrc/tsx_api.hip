@@ -213,8 +213,7 @@ static void ctx_free_device_mem(tsx_ctx* c) {
     for (void* p : ptrs) svc_free_dev(c->dev, p);
     svc_free_host(c->dev, c->h_segflag);
     svc_free_host(c->dev, c->h_descs);
-    svc_free_host(c->dev, c->h_verdicts);
-    svc_free_host(c->dev, c->h_records);
+    svc_free_host(c->dev, c->h_check);
     if (c->h_keyraw) { memset(c->h_keyraw, 0, 128); svc_free_host(c->dev, c->h_keyraw); }
     if (c->h_key) { memset(c->h_key, 0, sizeof(tsx_gcm_key)); svc_free_host(c->dev, c->h_key); }
     for (auto& e : c->ev) if (e) hipEventDestroy(e);

@@ -1,17 +1,16 @@
 // The batch pipelines of libtsxform's front end (tsx_api.hip: lifecycle, contexts, entry points): one planning step, then the compressing
-// forward chain as members of the compressor service (run_compress) or everything else as ordinary kernels (run_batch_inner), the small
-// kernels both queue, and verify on upload.  See include/tsxform.h for the contract.
+// forward chain as members of the compressor service (run_compress) or everything else as ordinary kernels (run_batch_inner), and the
+// small kernels both queue.  Where the checks of an upload run, and when their codes reach the descriptors, is decided here; what they
+// do is tsx_checks.hip's.  See include/tsxform.h for the contract.
 #include <algorithm>
 #include <chrono>
 #include <mutex>
-#include <new>
 #include <thread>
 #include <stdio.h>
 #include <string.h>
 #include <vector>
 
 #include "tsx_ctx.h"
-#include "zstd_dec_blocks.h"
 
 #define TSX_SUB_BYTES ((size_t)64 << 20) /* input bytes per sub-batch: >= 1000 workgroups of the GCM / CRC kernels */
 #define TSX_COMP_PIECES_MAX 8           /* members of one compressing host-memory batch (a completion counter + flag each) */
@@ -50,7 +49,7 @@ static uint8_t* device_alias_of_range(void* p, size_t bytes) {
 }
 
 // Waits for an event of a batch that is NOT the compressor's, with the safety net of svc_rotate.
-static hipError_t wait_event_watching(tsx_ctx* c, hipEvent_t ev) {
+hipError_t wait_event_watching(tsx_ctx* c, hipEvent_t ev) {
     const auto t0 = std::chrono::steady_clock::now();
     bool asked = false;
     for (;;) {
@@ -68,7 +67,7 @@ static hipError_t wait_event_watching(tsx_ctx* c, hipEvent_t ev) {
     }
 }
 
-static float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; hipEventElapsedTime(&ms, a, b); return ms; }
+float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; hipEventElapsedTime(&ms, a, b); return ms; }
 
 // ---- small glue kernels ---------------------------------------------------------------------------
 // Builds the GCM work items of a batch from the descriptors (and, after compression, the frame sizes),
@@ -153,6 +152,9 @@ __global__ __launch_bounds__(256) void wipe_key_kernel(uint4* __restrict__ d_key
     uint4 z; z.x = z.y = z.z = z.w = 0;
     for (uint32_t k = i; k < key_words16; k += gridDim.x * blockDim.x) d_key[k] = z;
     if (i < 8) d_keyraw[i] = z;
+}
+void launch_wipe_key(tsx_ctx* c, hipStream_t st) {
+    hipLaunchKernelGGL(wipe_key_kernel, dim3(6), dim3(256), 0, st, (uint4*)c->d_key, (uint32_t)(sizeof(tsx_gcm_key) / 16), (uint4*)c->d_keyraw);
 }
 
 __global__ void init_status_kernel(int32_t* status, uint32_t n) {
@@ -322,265 +324,6 @@ static int copy_back(const tsx_run& r, const tsx_sub& sb, size_t* packed_at, boo
     return TSX_OK;
 }
 
-// ======== verify on upload (TSX_VERIFY): everything of it, down to the next double rule ===============================================
-// (A section of this file rather than a unit of its own: verify_piece is called from the middle of run_compress and waits like a fetch
-//  - wait_event_watching, ev_ms, the context's events - so that as a unit it would have needed those declared across files as well as
-//  itself; as a section the one thing that crosses a file boundary is verifier_destroy.)
-// Verify on upload: ONE workspace per device (the literal and sequence arenas are ~21 MiB per 4 MiB chunk: too much per context with 32
-// callers in flight), created by the first verifying batch; a caller holds `mu` while a slice of its piece is verified in it.
-struct tsx_verifier {
-    std::mutex mu;
-    uint8_t* work = nullptr; size_t work_cap = 0;  // [slice descriptors and status words][chunk headers][arenas]
-    uint8_t* full = nullptr; size_t full_cap = 0;  // phase two: a chunk the block form did not take, restored in full
-};
-#define TSX_VERIFY_SLICE_BYTES ((size_t)3 << 29)   /* workspace budget of a slice: 1.5 GiB, ~73 chunks of 4 MiB (at least one chunk whatever its size) */
-#define TSX_V_WANTED 3                             /* fourth word of a chunk's verdict (zstd_dec_blocks.h): the chunk was TSX_OK and is to be verified */
-
-// What the verifier's kernels read, written on the device (the frame sizes exist only there): for chunk i of a slice, vdescs[i] describes
-// its frame to the block form's kernels (zstd_gpu.h: tsx_launch_zstd_verify_blocks), fdescs[i] to the chunk-serial decoder of phase two
-// (output at offset 0 of the verifier's buffer).  status == nullptr: the compressor waves own the status, in the descriptor itself.
-// no_blocks (test hook verify_force_fallback): the block form is told to leave every chunk alone.
-__global__ void verify_plan_kernel(const tsx_chunk_desc* __restrict__ descs, const int32_t* __restrict__ status, const uint32_t* __restrict__ zlen, uint32_t n,
-                                   tsx_chunk_desc* __restrict__ vdescs, tsx_chunk_desc* __restrict__ fdescs, int32_t* __restrict__ vstatus, int32_t* __restrict__ fstatus,
-                                   uint32_t* __restrict__ verdicts, int no_blocks) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const tsx_chunk_desc d = descs[i];
-    const bool wanted = (status ? status[i] : d.status) == TSX_OK;
-    tsx_chunk_desc v = d;
-    v.src_off = 0; v.src_len = zlen[i] + 28; v.dst_cap = d.src_len; v.dst_len = 0; v.status = TSX_OK;
-    v.dst_off = 0; fdescs[i] = v;
-    v.dst_off = d.src_off; vdescs[i] = v;
-    vstatus[i] = wanted && !no_blocks ? TSX_OK : TSX_E_INVAL;
-    fstatus[i] = TSX_OK;
-    verdicts[(size_t)i * ZB_VERDICT_WORDS + TSX_V_WANTED] = wanted ? 1u : 0u;
-}
-static_assert(ZB_VERDICT_WORDS == 4 && TSX_V_WANTED == 3, "a chunk's verdict: the verify kernel's three words and the plan kernel's");
-
-// test hooks verify_damage_*: one byte, one thread
-__global__ void verify_damage_kernel(uint8_t* p) { *p ^= 1; }
-
-// Phase two: the chunk restored in full by the chunk-serial decoder against its source.  V: the chunk's verdict words, zero on entry.
-__global__ __launch_bounds__(256) void verify_compare_kernel(const uint8_t* __restrict__ restored, const uint8_t* __restrict__ orig, const tsx_chunk_desc* __restrict__ fdesc,
-                                                             const int32_t* __restrict__ fstatus, uint32_t* __restrict__ V) {
-    const uint32_t len = fdesc->dst_cap;
-    bool diff = *fstatus != TSX_OK || fdesc->dst_len != len;          // (a frame the decoder rejects, or one of another size, restores nothing)
-    if (!diff) for (uint32_t p = blockIdx.x * 256 + threadIdx.x; p < len; p += gridDim.x * 256) diff |= restored[p] != orig[p];
-    if (diff) V[ZB_V_FAIL] = 1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) V[ZB_V_SEEN] = 1;
-}
-
-static std::mutex g_verifier_mu;                    // creation of a device's verifier
-static tsx_verifier* verifier_of(tsx_device* dev) {
-    std::lock_guard<std::mutex> lk(g_verifier_mu);
-    if (!dev->verifier) dev->verifier = new (std::nothrow) tsx_verifier;
-    return dev->verifier;
-}
-void verifier_destroy(tsx_device& d) {
-    if (d.verifier) { (void)hipFree(d.verifier->work); (void)hipFree(d.verifier->full); delete d.verifier; d.verifier = nullptr; }
-}
-
-// The context's verdict words, pinned: room for `chunks` chunks of ZB_VERDICT_WORDS words each.  *ok = false: the host has no memory for them.
-static int verdicts_reserve(tsx_ctx* c, size_t chunks, bool* ok) {
-    *ok = false;
-    if (c->verdicts_cap < chunks) {
-        svc_free_host(c->dev, c->h_verdicts); c->h_verdicts = nullptr; c->hd_verdicts = nullptr; c->verdicts_cap = 0;
-        const size_t cap = chunks + chunks / 4 + 16;
-        if (hipHostMalloc((void**)&c->h_verdicts, cap * ZB_VERDICT_WORDS * 4, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); c->h_verdicts = nullptr; return TSX_OK; }
-        HIPCHK(hipHostGetDevicePointer((void**)&c->hd_verdicts, c->h_verdicts, 0));
-        c->verdicts_cap = cap;
-    }
-    *ok = true;
-    return TSX_OK;
-}
-
-// Chunks [sb.lo, sb.lo + sb.n) - a member that has just completed - before anything of them is reported: vcode[i] = 0 (the frame restores
-// the chunk, or the chunk was not TSX_OK anyway), TSX_E_VERIFY, or TSX_E_NOMEM (never "not looked at").  The kernels are ordinary kernels
-// on a chip that compressor waves fill: the piece claims the reserved CUs like a fetch and waits with the fetch side's safety net.
-static int verify_piece(tsx_run& r, const tsx_sub& sb, bool self_status, int32_t* vcode) {
-    tsx_ctx* c = r.c;
-    tsx_device* dev = c->dev;
-    tsx_timing& t = c->timing;
-    for (uint32_t i = 0; i < sb.n; i++) vcode[sb.lo + i] = TSX_E_NOMEM;
-    int rc_ = TSX_OK;
-    tsx_verifier* const V = verifier_of(dev);
-    if (!V) return TSX_OK;
-    uint32_t max_len = 0;
-    for (uint32_t i = sb.lo; i < sb.lo + sb.n; i++) if (r.descs[i].src_len > max_len) max_len = r.descs[i].src_len;
-    const size_t per_chunk = tsx_zstd_verify_bytes(1, max_len) + 2 * sizeof(tsx_chunk_desc) + 8;
-    uint32_t slice = g_cfg.verify_slice_chunks ? g_cfg.verify_slice_chunks : (uint32_t)std::min<size_t>(TSX_VERIFY_SLICE_BYTES / per_chunk, sb.n);
-    if (slice < 1) slice = 1;
-    if (slice > sb.n) slice = sb.n;
-    bool have_verdicts = false;
-    if ((rc_ = verdicts_reserve(c, slice, &have_verdicts)) || !have_verdicts) return rc_;
-    svc_foreground_scope fg(dev);
-    std::lock_guard<std::mutex> lk(V->mu);
-    const size_t head = ((size_t)slice * (2 * sizeof(tsx_chunk_desc) + 8) + 255) & ~(size_t)255;
-    if (grow(dev, &V->work, &V->work_cap, head + tsx_zstd_verify_bytes(slice, max_len))) { (void)hipGetLastError(); return TSX_OK; }   // every chunk of the piece: TSX_E_NOMEM
-    const long long dsrc = g_cfg.verify_damage_src_chunk, dfrm = g_cfg.verify_damage_frame_chunk;
-    for (uint32_t lo = sb.lo; lo < sb.lo + sb.n; lo += slice) {
-        const uint32_t n = std::min(slice, sb.lo + sb.n - lo);
-        tsx_chunk_desc* const vdescs = (tsx_chunk_desc*)V->work; tsx_chunk_desc* const fdescs = vdescs + slice;
-        int32_t* const vstatus = (int32_t*)(fdescs + slice); int32_t* const fstatus = vstatus + slice;
-        const uint8_t* const frames = c->d_mid + (size_t)lo * c->mid_stride;
-        uint8_t* src_hit = nullptr;
-        memset(c->h_verdicts, 0, (size_t)n * ZB_VERDICT_WORDS * 4);
-        HIPCHK(hipEventRecord(c->ev[EV_VERIFY_BEGIN], c->st));
-        if (dsrc >= lo && dsrc < lo + n && g_cfg.verify_damage_src_off >= 0 && g_cfg.verify_damage_src_off < (long long)r.descs[dsrc].src_len) {
-            src_hit = (uint8_t*)r.d_src + r.descs[dsrc].src_off + g_cfg.verify_damage_src_off;
-            hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, c->st, src_hit); t.unzstd_launches++;
-        }
-        if (dfrm >= lo && dfrm < lo + n && g_cfg.verify_damage_frame_off >= 0 && g_cfg.verify_damage_frame_off < (long long)c->mid_stride) {
-            hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, c->st, c->d_mid + (size_t)dfrm * c->mid_stride + g_cfg.verify_damage_frame_off); t.unzstd_launches++;
-        }
-        hipLaunchKernelGGL(verify_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, c->st, (const tsx_chunk_desc*)((self_status ? c->hd_descs : c->d_descs) + lo),
-                           self_status ? (const int32_t*)nullptr : (const int32_t*)(c->d_status + lo), (const uint32_t*)(c->d_zlen + lo), n, vdescs, fdescs, vstatus, fstatus,
-                           c->hd_verdicts, g_cfg.verify_force_fallback ? 1 : 0);
-        t.unzstd_launches += 1 + tsx_launch_zstd_verify_blocks(c->st, frames, (uint64_t)c->mid_stride, vdescs, vstatus, n, max_len, r.d_src, V->work + head, c->hd_verdicts);
-        HIPCHK(hipEventRecord(c->ev[EV_VERIFY_END], c->st));
-        HIPCHK(wait_event_watching(c, c->ev[EV_VERIFY_END]));
-        t.unzstd_ms += ev_ms(c->ev[EV_VERIFY_BEGIN], c->ev[EV_VERIFY_END]);
-        // ---- phase two: what the block form did not take (above 16 MiB, more than 264 blocks, a frame it does not parse) is decoded in
-        // full, chunk by chunk, by the register-only build of the chunk-serial decoder (uploads are running: nothing here may need
-        // scratch), and compared byte for byte.  Rare, and allowed to synchronise.
-        for (uint32_t i = 0; i < n; i++) {
-            uint32_t* const W = c->h_verdicts + (size_t)i * ZB_VERDICT_WORDS;
-            const uint32_t j = lo + i;
-            if (!W[TSX_V_WANTED]) { vcode[j] = TSX_OK; continue; }
-            if (W[ZB_V_FAIL]) { vcode[j] = TSX_E_VERIFY; c->verify_block_form++; continue; }
-            if (W[ZB_V_SEEN] && !W[ZB_V_NOT_TAKEN]) { vcode[j] = TSX_OK; c->verify_block_form++; continue; }
-            c->verify_fallback++;
-            uint8_t* fp = V->full;
-            const int grc = grow(dev, &fp, &V->full_cap, (size_t)r.descs[j].src_len + 64);
-            V->full = fp;
-            if (grc) { (void)hipGetLastError(); continue; }            // vcode[j] stays TSX_E_NOMEM
-            W[ZB_V_FAIL] = 0; W[ZB_V_NOT_TAKEN] = 0; W[ZB_V_SEEN] = 0;
-            HIPCHK(hipEventRecord(c->ev[EV_VERIFY_BEGIN], c->st));
-            t.unzstd_launches += 1 + tsx_launch_zstd_decompress(c->st, c->d_mid + (size_t)j * c->mid_stride, 1, (uint64_t)c->mid_stride, fdescs + i, 1, V->full, fstatus + i,
-                                                                (uint8_t*)c->d_zwork + (size_t)j * tsx_zstd_workspace_bytes(1, 0), nullptr, 0, true);
-            const uint32_t blocks = std::max(1u, std::min(1024u, r.descs[j].src_len / 4096u));
-            hipLaunchKernelGGL(verify_compare_kernel, dim3(blocks), dim3(256), 0, c->st, (const uint8_t*)V->full, r.d_src + r.descs[j].src_off, (const tsx_chunk_desc*)(fdescs + i),
-                               (const int32_t*)(fstatus + i), c->hd_verdicts + (size_t)i * ZB_VERDICT_WORDS);
-            HIPCHK(hipEventRecord(c->ev[EV_VERIFY_END], c->st));
-            HIPCHK(wait_event_watching(c, c->ev[EV_VERIFY_END]));
-            t.unzstd_ms += ev_ms(c->ev[EV_VERIFY_BEGIN], c->ev[EV_VERIFY_END]);
-            vcode[j] = W[ZB_V_FAIL] || !W[ZB_V_SEEN] ? TSX_E_VERIFY : TSX_OK;
-        }
-        if (src_hit) { hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, c->st, src_hit); HIPCHK(hipStreamSynchronize(c->st)); }
-    }
-    HIPCHK(hipGetLastError());
-    return TSX_OK;
-}
-
-// ---- verify on upload, GCM stage (TSX_VERIFY_GCM) of a compressing batch ---------------------------------------------------------------
-// The verifier's work items for chunks 0 .. n - 1 of a piece, from the piece's descriptors in pinned memory as the host has left them
-// (status, dst_off, dst_len, iv: the waves', or separate_finish's, with the Zstandard verifier's verdicts applied) and the frame sizes:
-// reference = the chunk's frame in the staging buffer, delivered = the chunk's slot.  hd_key != nullptr (fused chain: the schedule exists
-// in pinned memory only): the kernel brings it to the device as begin_batch_kernel does - a copy would be a blit that waits behind a chip
-// full of compressor waves.
-__global__ __launch_bounds__(256) void plan_gcm_verify_kernel(const tsx_chunk_desc* __restrict__ descs, const uint32_t* __restrict__ zlen, uint64_t mid_stride, uint32_t n,
-                                                              tsx_gcm_chunk* __restrict__ g, const uint4* __restrict__ hd_key, uint4* __restrict__ d_key, uint32_t key_words16) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const tsx_chunk_desc d = descs[i];
-        tsx_gcm_chunk c;
-        c.in_off = (uint64_t)i * mid_stride; c.out_off = d.dst_off; c.len = zlen[i];
-        for (int k = 0; k < 12; k++) c.iv[k] = d.iv[k];
-        c.skip = d.status != TSX_OK ? 1 : d.dst_len != c.len + 28 ? 2 : 0;
-        g[i] = c;
-    }
-    if (hd_key) for (uint32_t k = i; k < key_words16; k += gridDim.x * blockDim.x) d_key[k] = hd_key[k];
-}
-
-// Chunks [sb.lo, sb.lo + sb.n) - a member whose GCM stage has run (in its waves, or in separate_finish) - before anything of them is
-// reported or copied back: gcode[i] = 0 (delivered bytes decrypt to the frame and carry its tag, or the chunk was not TSX_OK anyway),
-// TSX_E_VERIFY, or TSX_E_NOMEM.  Ordinary kernels next to the service, as verify_piece's: the piece counts as a fetch having been seen
-// and waits with the fetch side's safety net.  The test hook verify_damage_out_* acts here, flag or no flag.
-static int gcm_verify_piece(tsx_run& r, const tsx_sub& sb, int32_t* gcode) {
-    tsx_ctx* c = r.c;
-    tsx_device* dev = c->dev;
-    tsx_timing& t = c->timing;
-    const bool verify = (r.flags & TSX_VERIFY_GCM) != 0;
-    const long long dj = g_cfg.verify_damage_out_chunk, doff = g_cfg.verify_damage_out_off;
-    const bool damage = dj >= sb.lo && dj < sb.lo + sb.n && doff >= 0 && c->h_descs[dj].status == TSX_OK && doff < (long long)c->h_descs[dj].dst_len;
-    if (!verify && !damage) return TSX_OK;
-    if (verify) {
-        for (uint32_t i = 0; i < sb.n; i++) gcode[sb.lo + i] = c->h_descs[sb.lo + i].status == TSX_OK ? TSX_E_NOMEM : TSX_OK;
-        bool have_verdicts = false;
-        const int rc = verdicts_reserve(c, (sb.n + ZB_VERDICT_WORDS - 1) / ZB_VERDICT_WORDS, &have_verdicts);      // one word per chunk
-        if (rc || !have_verdicts) return rc;
-        memset(c->h_verdicts, 0, (size_t)sb.n * 4);
-    }
-    svc_foreground_scope fg(dev);
-    HIPCHK(hipEventRecord(c->ev[EV_VERIFY_BEGIN], c->st));
-    if (damage) { hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, c->st, r.d_dst + c->h_descs[dj].dst_off + doff); t.gcm_launches++; }
-    if (verify) {
-        const bool stage_key = r.fuse_stages;                           // (separate stages: separate_finish has uploaded it, run_batch wipes it)
-        const uint32_t kw = (uint32_t)(sizeof(tsx_gcm_key) / 16);
-        if (stage_key) { c->key_staged = true; c->key_wiped = false; }   // (run_batch clears d_key itself when the batch fails before this piece's wipe)
-        hipLaunchKernelGGL(plan_gcm_verify_kernel, dim3(std::max((sb.n + 255u) / 256u, stage_key ? 6u : 1u)), dim3(256), 0, c->st, (const tsx_chunk_desc*)(c->hd_descs + sb.lo),
-                           (const uint32_t*)(c->d_zlen + sb.lo), (uint64_t)c->mid_stride, sb.n, c->d_gchunks + sb.lo, stage_key ? (const uint4*)c->hd_key : (const uint4*)nullptr,
-                           (uint4*)c->d_key, stage_key ? kw : 0u);
-        tsx_launch_gcm_verify(c->st, dev->d_aes, c->d_key, c->d_gchunks + sb.lo, c->hd_descs + sb.lo, sb.n, (uint32_t)tsx_transformed_bound(r.max_len, TSX_COMPRESS),
-                              c->d_mid + (size_t)sb.lo * c->mid_stride, r.d_dst, c->d_partials + (size_t)sb.lo * c->partials_per_chunk, c->hd_verdicts, nullptr);
-        t.gcm_launches += 3;
-        if (stage_key) {                                                // the schedule does not stay on the device between the pieces
-            hipLaunchKernelGGL(wipe_key_kernel, dim3(6), dim3(256), 0, c->st, (uint4*)c->d_key, kw, (uint4*)c->d_keyraw); t.gcm_launches++;
-        }
-    }
-    HIPCHK(hipEventRecord(c->ev[EV_VERIFY_END], c->st));
-    HIPCHK(wait_event_watching(c, c->ev[EV_VERIFY_END]));
-    if (verify) {
-        if (r.fuse_stages) c->key_wiped = true;
-        t.gcm_ms += ev_ms(c->ev[EV_VERIFY_BEGIN], c->ev[EV_VERIFY_END]);
-        for (uint32_t i = 0; i < sb.n; i++)                             // (a chunk that was TSX_OK and has no verdict has not been examined: not reported TSX_OK)
-            if (c->h_descs[sb.lo + i].status == TSX_OK) gcode[sb.lo + i] = c->h_verdicts[i] == TSX_GV_SEEN ? TSX_OK : TSX_E_VERIFY;
-    }
-    HIPCHK(hipGetLastError());
-    return TSX_OK;
-}
-// ======== end of verify on upload ======================================================================================================
-
-// ======== record-batch validation (TSX_VALIDATE_RECORDS) ================================================================================
-// The source of the whole batch - every piece's input has landed behind `staged` (nullptr: it was on the device to begin with) - as ONE
-// stream of Kafka record batches (records.hip): rcode[i] = 0 (no invalid batch begins in or before chunk i), TSX_E_RECORDS, or TSX_E_NOMEM
-// (never "not looked at").  Two ordinary kernels on the context's stream, next to whatever the batch's own stages are doing (a compressing
-// batch's waves have a second of work per chunk in front of them): the batch claims the reserved CUs like a fetch and waits with the
-// fetch side's safety net.  Everything the kernels say comes back through the context's pinned block.
-static int records_validate(tsx_run& r, hipEvent_t staged, int32_t* rcode) {
-    tsx_ctx* c = r.c;
-    for (uint32_t i = 0; i < r.n; i++) rcode[i] = TSX_E_NOMEM;
-    const size_t need = tsx_records_block_bytes(r.n);
-    if (c->records_cap < need) {
-        svc_free_host(c->dev, c->h_records); c->h_records = nullptr; c->hd_records = nullptr; c->records_cap = 0;
-        const size_t cap = need + need / 4 + 256;
-        if (hipHostMalloc((void**)&c->h_records, cap, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); c->h_records = nullptr; return TSX_OK; }
-        HIPCHK(hipHostGetDevicePointer((void**)&c->hd_records, c->h_records, 0));
-        c->records_cap = cap;
-    }
-    tsx_records_block_fill(c->h_records, r.descs, r.n);
-    svc_foreground_scope fg(c->dev);
-    if (staged) HIPCHK(hipStreamWaitEvent(c->st, staged, 0));
-    HIPCHK(hipEventRecord(c->ev[EV_RECORDS_BEGIN], c->st));
-    tsx_launch_records(c->st, c->dev->d_crc, r.d_src, c->hd_records, r.n);
-    HIPCHK(hipEventRecord(c->ev[EV_RECORDS_END], c->st));
-    HIPCHK(wait_event_watching(c, c->ev[EV_RECORDS_END]));
-    HIPCHK(hipGetLastError());
-    const tsx_rec_block b = tsx_records_block_at(c->h_records, r.n);
-    if (!__atomic_load_n(&b.head->done, __ATOMIC_ACQUIRE)) return TSX_OK;
-    for (uint32_t i = 0; i < r.n; i++) rcode[i] = b.verdicts[i];
-    tsx_records_info& o = c->records;
-    o.batches = b.head->batches; o.compressed_batches = b.head->compressed; o.first_bad_pos = b.head->first_bad_pos;
-    o.first_bad_reason = b.head->first_bad_reason; o.repaired_chunks = b.head->repaired;
-    o.ms = ev_ms(c->ev[EV_RECORDS_BEGIN], c->ev[EV_RECORDS_END]);
-    return TSX_OK;
-}
-// ... into chunks [lo, lo + n) of `descs`, before they reach the caller: a chunk that already carries another error keeps it
-static void records_merge(tsx_chunk_desc* descs, const int32_t* rcode, uint32_t lo, uint32_t n) {
-    for (uint32_t i = lo; i < lo + n; i++) if (rcode[i] && descs[i].status == TSX_OK) { descs[i].status = rcode[i]; descs[i].dst_len = 0; }
-}
-// ======== end of record-batch validation ===============================================================================================
-
 // ---- the compressing forward chain: members of the device's service ---------------------------------------------------------------------
 // Zero-copy output (round 4).  The wave that finishes a chunk writes its bytes straight into the caller's buffer over PCIe when the device
 // can address ALL of it (device_alias_of_range): posted writes of a few ms of a second-long wave, released to system scope before the
@@ -644,12 +387,10 @@ static int run_compress(tsx_run& r) {
     memset(&c->timing, 0, sizeof c->timing);
     tsx_timing& t = c->timing;
     c->verify_block_form = 0; c->verify_fallback = 0;
-    std::vector<int32_t> vcode;                                         // TSX_VERIFY: per chunk, what the verifier has to say (0: nothing)
-    if (r.flags & TSX_VERIFY) vcode.assign(n, 0);
-    std::vector<int32_t> gcode;                                         // TSX_VERIFY_GCM: the same of the GCM verifier
-    if (r.flags & TSX_VERIFY_GCM) gcode.assign(n, 0);
-    std::vector<int32_t> rcode;                                         // TSX_VALIDATE_RECORDS: the same of the record-batch validator
-    if (r.flags & TSX_VALIDATE_RECORDS) rcode.assign(n, 0);
+    // per chunk, what a check has to say (0: nothing; tsx_checks.hip): the two verifiers' of a piece, one after the other; the record
+    // validator's of the whole batch
+    const bool zverify = r.flags & TSX_VERIFY, gverify = r.flags & TSX_VERIFY_GCM, records = r.flags & TSX_VALIDATE_RECORDS;
+    std::vector<int32_t> vcode(zverify || gverify ? n : 0, 0), rcode(records ? n : 0, 0);
     // ---- the pieces ----
     std::vector<tsx_sub> subs;
     {
@@ -726,7 +467,7 @@ static int run_compress(tsx_run& r) {
     }
     // ---- record-batch validation: every piece's input has landed (the last piece was published when its own had); the validator's two
     // kernels run while the service compresses, and their verdicts are in hand before the first piece is handed back ----
-    if (!rcode.empty() && (rc = records_validate(r, r.host ? c->sub_ev[ns - 1][SUB_STAGED_IN] : nullptr, rcode.data()))) return abandon_all(rc);
+    if (records && (rc = records_validate(r, r.host ? c->sub_ev[ns - 1][SUB_STAGED_IN] : nullptr, rcode.data()))) return abandon_all(rc);
     // ---- completions, in order; a piece's bytes travel back (or are packed down) while the later pieces still run ----
     size_t packed_at = 0; bool packed_full = false;
     const auto t_pub = std::chrono::steady_clock::now();
@@ -736,15 +477,16 @@ static int run_compress(tsx_run& r) {
         svc_retire(dev, ids[k], false);
         ids[k] = 0;
         if (k + 1 == ns) t.zstd_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_pub).count();
-        // verify on upload: the piece's frames and their source chunks are both still on the device; the later pieces keep compressing
-        if (!vcode.empty() && (rc = verify_piece(r, sb, self_status, vcode.data()))) return abandon_all(rc);
+        // verify on upload: the piece's frames and their source chunks are both still on the device; the later pieces keep compressing.
+        // Its codes are applied behind separate_finish, which overwrites h_descs
+        if (zverify && (rc = verify_piece(r, sb, self_status, vcode.data()))) return abandon_all(rc);
         if (!self_status && (rc = separate_finish(r, sb, k == 0))) return abandon_all(rc);
-        if (!vcode.empty()) for (uint32_t i = sb.lo; i < sb.lo + sb.n; i++) if (vcode[i] && c->h_descs[i].status == TSX_OK) { c->h_descs[i].status = vcode[i]; c->h_descs[i].dst_len = 0; }
+        if (zverify) check_apply(c->h_descs, vcode.data(), sb.lo, sb.n);
         // verify on upload, GCM stage: the piece's delivered bytes, before its descriptors reach the caller and before copy_back / pack_chunks
-        // move them (chunks the Zstandard verifier has just failed are skipped)
-        if (r.enc && (rc = gcm_verify_piece(r, sb, gcode.data()))) return abandon_all(rc);
-        if (!gcode.empty()) for (uint32_t i = sb.lo; i < sb.lo + sb.n; i++) if (gcode[i] && c->h_descs[i].status == TSX_OK) { c->h_descs[i].status = gcode[i]; c->h_descs[i].dst_len = 0; }
-        if (!rcode.empty()) records_merge(c->h_descs, rcode.data(), sb.lo, sb.n);
+        // move them (chunks the Zstandard verifier has just failed are skipped; without the flag only its test hook acts)
+        if (r.enc && (rc = gcm_verify_piece(r, sb, vcode.data()))) return abandon_all(rc);
+        if (gverify) check_apply(c->h_descs, vcode.data(), sb.lo, sb.n);
+        if (records) check_apply(c->h_descs, rcode.data(), sb.lo, sb.n);
         memcpy(r.descs + sb.lo, c->h_descs + sb.lo, (size_t)sb.n * sizeof(tsx_chunk_desc));
         if (r.zc_dst) {
             // the bytes are where they belong; a packed batch is packed down in place.  (compress_zero_copy_ok: dst_size >= out_bytes, the
@@ -806,18 +548,7 @@ static int launch_stages(const tsx_run& r, const tsx_sub& sb, hipEvent_t* e, hip
         HIPCHK(hipEventRecord(e[SUB_STAGE2], st));
         if (r.enc) {
             launch_gcm_stage(r, st, lo, n, 0, 0, 0, r.max_len, r.d_src, r.d_dst);
-            // test hook verify_damage_out_*: an encrypt-only chunk that fits its slot delivers src_len + 28 bytes
-            const long long dj = g_cfg.verify_damage_out_chunk, doff = g_cfg.verify_damage_out_off;
-            if (dj >= lo && dj < lo + n && doff >= 0 && doff < (long long)r.descs[dj].src_len + 28 && (uint64_t)r.descs[dj].src_len + 28 <= r.descs[dj].dst_cap) {
-                hipLaunchKernelGGL(verify_damage_kernel, dim3(1), dim3(1), 0, st, r.d_dst + r.descs[dj].dst_off + doff); t.gcm_launches++;
-            }
-            // verify on upload, GCM stage: in stream behind the stage, on the work items plan_gcm_kernel has made (in: the source chunk on the
-            // device, out: where the chunk was delivered - with zero-copy output the caller's buffer); a chunk that fails is TSX_E_VERIFY in
-            // d_status before publish_status_kernel reports it
-            if (flags & TSX_VERIFY_GCM) {
-                tsx_launch_gcm_verify(st, c->dev->d_aes, c->d_key, c->d_gchunks + lo, dd, n, r.max_len, r.d_src, r.d_dst, dpart, nullptr, ds);
-                t.gcm_launches += 2;
-            }
+            gcm_verify_in_stream(r, sb, st);                            // TSX_VERIFY_GCM (and its test hook): behind the stage, in front of the publication
         } else launch_copy_chunks(r, st, lo, n, 0, r.d_src);
         hipLaunchKernelGGL(publish_status_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dd, (const int32_t*)ds, n, hm);
     } else {
@@ -952,7 +683,7 @@ static int run_batch_inner(tsx_run& r) {
         }
         HIPCHK(wait_event_watching(c, c->sub_ev[k][SUB_DONE]));              // descriptors of piece k are on the host
         memcpy(r.descs + sb.lo, c->h_descs + sb.lo, (size_t)sb.n * sizeof(tsx_chunk_desc));
-        if (!rcode.empty()) records_merge(r.descs, rcode.data(), sb.lo, sb.n);
+        if (!rcode.empty()) check_apply(r.descs, rcode.data(), sb.lo, sb.n);
         if (r.zc_dst) return TSX_OK;                                    // the bytes are in the caller's buffer already
         if (r.host && r.mode != 2) return copy_back(r, sb, &packed_at, &packed_full, (out2 && (k & 1)) ? c->st_out2 : c->st_out);
         return TSX_OK;
@@ -978,7 +709,7 @@ static int run_batch_inner(tsx_run& r) {
     if (r.enc) {
         // the key material leaves the device behind the batch's last kernel (every piece's chain has been joined into st above); the pinned
         // originals are wiped by run_batch
-        hipLaunchKernelGGL(wipe_key_kernel, dim3(6), dim3(256), 0, st, (uint4*)c->d_key, (uint32_t)(sizeof(tsx_gcm_key) / 16), (uint4*)c->d_keyraw);
+        launch_wipe_key(c, st);
         c->key_wiped = true;
     }
     HIPCHK(hipEventRecord(c->ev[EV_END], st));

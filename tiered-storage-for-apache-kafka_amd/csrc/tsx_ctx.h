@@ -1,6 +1,6 @@
 // What the front end's translation units share about a context and a batch (tsx_api.hip: lifecycle, contexts, the pool, entry points;
-// tsx_batch.hip: the batch pipelines and verify on upload): the context record, the names of its events, what one batch carries through
-// the pipelines, and the few functions the two call across.
+// tsx_batch.hip: the batch pipelines; tsx_checks.hip: the checks of an upload): the context record, the names of its events, what one
+// batch carries through the pipelines, and the few functions the units call across.
 #pragma once
 #include "tsx_host.h"
 #include "tsx_service.h"
@@ -12,8 +12,7 @@ enum {
     EV_BEGIN, EV_END,                   // on st: the batch's first and last kernel (tsx_timing.total_ms)
     EV_H2D_FIRST,                       // on the copy-in stream, in front of the first piece's input copy
     EV_D2H_LAST,                        // on the copy-out stream, behind the last piece's output copies
-    EV_VERIFY_BEGIN, EV_VERIFY_END,     // on st: one slice (or one phase-two chunk) of verify on upload, in the middle of a compressing batch
-    EV_RECORDS_BEGIN, EV_RECORDS_END,   // on st: the record-batch validator's two kernels (tsx_records_info.ms)
+    EV_CHECK_BEGIN, EV_CHECK_END,       // on st: one timed wait of a check of an upload (tsx_checks.hip; the calling thread runs one at a time)
     EV_COUNT
 };
 // tsx_ctx::sub_ev[k][]: the events of piece k
@@ -66,12 +65,11 @@ struct tsx_ctx {
     bool last_zero_copy = false;                   // ... and whether its waves wrote into the caller's buffer (test hook)
     bool key_wiped = false;                        // the batch's own wipe_key_kernel has cleared d_key / d_keyraw
     bool key_staged = false;                       // a fused compressing batch's GCM verifier has brought the key schedule to d_key (wiped behind every piece)
-    // verify on upload (TSX_VERIFY, and TSX_VERIFY_GCM of a compressing batch): the verifier's words per chunk of a slice, pinned, and as the device addresses them (created by the first verifying batch)
-    uint32_t* h_verdicts = nullptr; uint32_t* hd_verdicts = nullptr; size_t verdicts_cap = 0;
-    // record-batch validation (TSX_VALIDATE_RECORDS): the validator's block (tsx_internal.h: tsx_rec_block), pinned, and as the device addresses it
-    // (created by the first validating batch); what the last batch found
-    uint8_t* h_records = nullptr; uint8_t* hd_records = nullptr; size_t records_cap = 0;
-    tsx_records_info records{};
+    // the checks of an upload (tsx_checks.hip): the block their kernels answer in, pinned, and as the device addresses it (created by the
+    // first checking batch; one check at a time: the Zstandard verifier's four words per chunk of a slice, the GCM verifier's one word
+    // per chunk of a piece, the record validator's tsx_rec_block)
+    uint8_t* h_check = nullptr; uint8_t* hd_check = nullptr; size_t check_cap = 0;
+    tsx_records_info records{};                    // what the last batch's record validator found
     uint32_t verify_block_form = 0, verify_fallback = 0;   // chunks of the last batch the block form judged / that were decoded in full (test hook)
 };
 
@@ -104,12 +102,28 @@ static inline bool dec_use_blocks(uint32_t n, uint32_t max_out) { return n <= g_
 // ctx_reserve; an allocation that fails drains the device's idle pooled contexts and is tried again
 int reserve_or_drain(tsx_ctx* c, uint32_t n, uint32_t max_len, uint32_t max_out, uint32_t flags, bool host_mem, size_t in_bytes, size_t out_bytes);
 
-// ---- tsx_batch.hip, for the entry points ----
+// ---- tsx_batch.hip, for the entry points and the checks ----
 int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n, const void* src, size_t src_size, void* dst,
               size_t dst_size, int mem_kind, int mode /*0 transform, 1 detransform, 2 crc only*/, bool pooled = false);
 // the host ranges tsx_host_register has pinned (zero-copy output asks: device_alias_of_range); forget_all: tsx_shutdown
 void registered_range_add(void* p, size_t bytes);
 void registered_range_remove(void* p);
 void registered_range_forget_all();
+// wait for an event of a batch of ordinary kernels, with the safety net of svc_rotate; milliseconds between two events that have passed
+hipError_t wait_event_watching(tsx_ctx* c, hipEvent_t ev);
+float ev_ms(hipEvent_t a, hipEvent_t b);
+// wipe_key_kernel on st: the key schedule and the raw key leave the device
+void launch_wipe_key(tsx_ctx* c, hipStream_t st);
+
+// ---- tsx_checks.hip, for the pipelines (and tsx_api.hip: verifier_destroy) ----
+// One code per chunk into code[] (indexed like the batch: 0, the check's error, or TSX_E_NOMEM), waited for: the Zstandard verifier and
+// the GCM verifier of chunks [sb.lo, sb.lo + sb.n) of a compressing batch, the record validator of a whole batch
+int verify_piece(tsx_run& r, const tsx_sub& sb, bool self_status, int32_t* code);
+int gcm_verify_piece(tsx_run& r, const tsx_sub& sb, int32_t* code);
+int records_validate(tsx_run& r, hipEvent_t staged, int32_t* code);
+// the GCM verifier of an encrypt-only piece: queued on st behind the piece's GCM stage, its codes go to d_status on the device
+void gcm_verify_in_stream(const tsx_run& r, const tsx_sub& sb, hipStream_t st);
+// code[lo .. lo + n) reach descs[lo .. lo + n): a chunk that already carries an error keeps it, one that takes a code delivers nothing
+void check_apply(tsx_chunk_desc* descs, const int32_t* code, uint32_t lo, uint32_t n);
 // the device's verify-on-upload workspace goes with the device (device current)
 void verifier_destroy(tsx_device& d);

@@ -1,5 +1,6 @@
 // What the host-side translation units share (tsx_api.hip: devices, contexts, entry points; tsx_batch.hip: the batch pipelines;
-// tsx_service.hip: the compressor service): the configuration, error reporting, the device record.  (Contexts and batches: tsx_ctx.h.)
+// tsx_checks.hip: the checks of an upload; tsx_service.hip: the compressor service): the configuration, error reporting, the device
+// record.  (Contexts and batches: tsx_ctx.h.)
 #pragma once
 #include <memory>
 #include <utility>
@@ -60,7 +61,7 @@ struct tsx_device_scope {
 };
 
 struct tsx_ctx;
-struct tsx_verifier;                                         // tsx_batch.hip: the device's verify-on-upload workspace
+struct tsx_verifier;                                         // tsx_checks.hip: the device's verify-on-upload workspace
 struct tsx_service;                                          // tsx_service.hip: nobody else looks inside
 struct tsx_service_delete { void operator()(tsx_service* s) const; };
 
