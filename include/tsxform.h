@@ -170,6 +170,15 @@ typedef struct tsx_batch_params {
  * whether they are 1.5.6's bytes is settled where that library exists: tests/golden/make_vectors_from_lib.py + tests/test_golden.py. */
 #define TSX_ZSTD_PROFILE_1_5_6 0u
 #define TSX_ZSTD_PROFILE_1_5_7 1u
+/* TSX_ZSTD_PROFILE_DEVICE: standard Zstandard frames (RFC 8878) that are NOT any libzstd's bytes.  The frame header, the 128 KiB blocks
+ * (cut at fixed 128 KiB, no pre-splitter), the window (at most 1 << 21), the raw and RLE fallbacks, the entropy stages, the content
+ * checksum on TSX_ZSTD_CHECKSUM and tsx_transformed_bound are those of the other profiles; the match finder is a parse shaped for the
+ * wave: 64 lanes parse 64 slices of a block side by side, with 64 table probes in flight where the exact parse has one dependency chain.
+ * Every Zstandard decoder reads the frames, and a frame is a function of the chunk's bytes and the flags only - the same on every run,
+ * wave and device.  What it is not: byte-identical to any library, as small as level 3's frames (DESIGN.md has the ratios), or
+ * selectable by level - zstd_level must be 0 with it, anything else is TSX_E_UNSUPPORTED (levels name libzstd's parsers).
+ * tsx_detransform_batch ignores the profile.  TSX_VERIFY is recommended with it: the frames have no library to be compared against. */
+#define TSX_ZSTD_PROFILE_DEVICE 2u
 
 typedef struct tsx_ctx tsx_ctx;
 
@@ -183,7 +192,7 @@ typedef struct tsx_timing {
 
 /* ---- library lifetime ---------------------------------------------------------------------- */
 uint32_t    tsx_abi_version(void);
-const char* tsx_version(void);           /* "tsxform x.y (gfx950; zstd parity target 1.5.7/1.5.6, levels 1-3)" */
+const char* tsx_version(void);           /* "tsxform x.y (gfx950; zstd parity target 1.5.7/1.5.6, levels 1-3, device profile)" */
 const char* tsx_strerror(int code);
 /* device_ids == NULL: use devices 0..device_count-1; device_count <= 0: all visible devices.  An id may be listed more than once
  * (the same GPU as several logical devices, each with its own pools and compressor service: tests of the multi-device dispatch).

@@ -62,7 +62,9 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
     /**
      * @param zstdProfile TsxNative.ZSTD_PROFILE_1_5_6 (the libzstd inside the reference's zstd-jni 1.5.6-9, core/build.gradle:29)
      *                    or ZSTD_PROFILE_1_5_7; configuration key {@code gpu.zstd.profile} - INTEGRATION.md says what each
-     *                    profile has been compared with
+     *                    profile has been compared with.  Or ZSTD_PROFILE_DEVICE ({@code gpu.zstd.profile=device}): standard frames
+     *                    from the GPU-shaped parse, no library's bytes; a Zstd level together with it is refused, and
+     *                    {@code compression.zstd.verify=true} is recommended with it
      * @param segmentHash any stable hash of the segment (e.g. of its RemoteLogSegmentId): its batches go to GPU
      *                    floorMod(segmentHash, deviceCount) so that the node's GPUs are all used and one segment stays on one
      * @param readAhead   while the consumer (TransformFinisher -> the uploader) drains batch k, batch k + 1 is already read
@@ -180,8 +182,12 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
         this.keyAndAad = keyAndAad;
         this.batchChunks = batchChunks;
         this.random = random;
-        if (zstdProfile != TsxNative.ZSTD_PROFILE_1_5_6 && zstdProfile != TsxNative.ZSTD_PROFILE_1_5_7) {
+        if (zstdProfile != TsxNative.ZSTD_PROFILE_1_5_6 && zstdProfile != TsxNative.ZSTD_PROFILE_1_5_7
+            && zstdProfile != TsxNative.ZSTD_PROFILE_DEVICE) {
             throw new IllegalArgumentException("unknown Zstd profile " + zstdProfile);
+        }
+        if (zstdProfile == TsxNative.ZSTD_PROFILE_DEVICE && zstdLevel != 0) {
+            throw new IllegalArgumentException("the device Zstd profile has no levels, compression.zstd.level " + zstdLevel + " given");
         }
         this.zstdProfile = zstdProfile;
         this.readAhead = readAhead;

@@ -247,8 +247,12 @@ public class GpuTransformFinisher {
         if (originalFileSize < 0) {
             throw new IllegalArgumentException("originalFileSize must be non-negative, " + originalFileSize + " given");
         }
-        if (zstdProfile != TsxNative.ZSTD_PROFILE_1_5_6 && zstdProfile != TsxNative.ZSTD_PROFILE_1_5_7) {
+        if (zstdProfile != TsxNative.ZSTD_PROFILE_1_5_6 && zstdProfile != TsxNative.ZSTD_PROFILE_1_5_7
+            && zstdProfile != TsxNative.ZSTD_PROFILE_DEVICE) {
             throw new IllegalArgumentException("unknown Zstd profile " + zstdProfile);
+        }
+        if (zstdProfile == TsxNative.ZSTD_PROFILE_DEVICE && zstdLevel != 0) {
+            throw new IllegalArgumentException("the device Zstd profile has no levels, compression.zstd.level " + zstdLevel + " given");
         }
         this.compress = compress;
         this.keyAndAad = keyAndAad;

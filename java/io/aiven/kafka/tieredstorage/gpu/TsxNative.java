@@ -63,6 +63,24 @@ public final class TsxNative {
      */
     public static final int ZSTD_PROFILE_1_5_6 = 0;
     public static final int ZSTD_PROFILE_1_5_7 = 1;
+    /**
+     * TSX_ZSTD_PROFILE_DEVICE: standard Zstandard frames from a parse shaped for the GPU (64 lanes parse 64 slices of a block side by
+     * side) - no libzstd's bytes, larger than level 3's frames, readable by every Zstandard decoder, the same bytes for the same chunk
+     * on every run.  It has no levels: {@code compression.zstd.level} together with it is refused.  {@code compression.zstd.verify=true}
+     * is recommended with it: its frames have no library to be compared with, and verify on upload decodes every one of them against
+     * its chunk before the segment is reported.
+     */
+    public static final int ZSTD_PROFILE_DEVICE = 2;
+
+    /** The value of the configuration key {@code gpu.zstd.profile}: {@code 1.5.6}, {@code 1.5.7} or {@code device}. */
+    public static int zstdProfileOf(final String configured) {
+        switch (configured) {
+            case "1.5.6": return ZSTD_PROFILE_1_5_6;
+            case "1.5.7": return ZSTD_PROFILE_1_5_7;
+            case "device": return ZSTD_PROFILE_DEVICE;
+            default: throw new IllegalArgumentException("gpu.zstd.profile must be 1.5.6, 1.5.7 or device, " + configured + " given");
+        }
+    }
 
     static {
         System.loadLibrary("tsxform_jni");   // links libtsxform.so

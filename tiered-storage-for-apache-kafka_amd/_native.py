@@ -22,7 +22,7 @@ OK, E_INVAL, E_DEVICE, E_NOMEM, E_DST_TOO_SMALL, E_TAG_MISMATCH, E_BAD_FRAME, E_
     0, -1, -2, -3, -4, -5, -6, -7, -8, -9
 E_VERIFY = -10           # per chunk, under VERIFY: the frame written for the chunk does not restore it
 E_RECORDS = -11          # per chunk, under VALIDATE_RECORDS: an invalid record batch begins in or before this chunk
-ZSTD_PROFILE_1_5_6, ZSTD_PROFILE_1_5_7 = 0, 1
+ZSTD_PROFILE_1_5_6, ZSTD_PROFILE_1_5_7, ZSTD_PROFILE_DEVICE = 0, 1, 2
 ABI_VERSION = 4          # TSX_ABI_VERSION of include/tsxform.h these prototypes were written against
 
 

@@ -189,7 +189,7 @@ extern "C" int tsx_init_ex(int device_count, const int* device_ids, const tsx_co
     char* vb = g_version_buf[g_version_gen++ & 1];
     const svc_geometry sg = svc_geometry_of(g_devs[0]);
     snprintf(vb, sizeof g_version_buf[0],
-             "tsxform 0.5 (gfx950 HIP; CRC32C, AES-256-GCM, Zstd frames of levels 1-3; zstd parity target libzstd 1.5.7 / 1.5.6 profile; %d device(s): %s; "
+             "tsxform 0.5 (gfx950 HIP; CRC32C, AES-256-GCM, Zstd frames of levels 1-3; zstd parity target libzstd 1.5.7 / 1.5.6 profile, device profile; %d device(s): %s; "
              "compressor service: %u waves, %u of %u CUs reserved for fetches)",
              (int)g_devs.size(), g_devs[0].name, sg.waves, sg.cus_reserved, sg.cus);
     g_version.store(vb, std::memory_order_release);

@@ -765,7 +765,10 @@ int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs,
     if (mode != 2) {
         if (params->aad_len > 64) return TSX_E_INVAL;
         if ((flags & TSX_COMPRESS) && !(params->zstd_level >= 0 && params->zstd_level <= 3)) return TSX_E_UNSUPPORTED;   // 0 = 3 (the library default), 1, 2, 3
-        if ((flags & TSX_COMPRESS) && params->zstd_profile > TSX_ZSTD_PROFILE_1_5_7) return TSX_E_UNSUPPORTED;
+        if ((flags & TSX_COMPRESS) && params->zstd_profile > TSX_ZSTD_PROFILE_DEVICE) return TSX_E_UNSUPPORTED;
+        // the device profile has one parse - levels name libzstd's parsers; a fetch ignores the profile (callers build one parameter block for
+        // both directions, and a Zstandard decoder reads every profile's frames)
+        if (mode == 0 && (flags & TSX_COMPRESS) && params->zstd_profile == TSX_ZSTD_PROFILE_DEVICE && params->zstd_level != 0) return TSX_E_UNSUPPORTED;
     }
     memset(&c->records, 0, sizeof c->records); c->records.first_bad_pos = ~0ull;
     if (n == 0) return TSX_OK;

@@ -31,7 +31,8 @@
 // This is byte-stream work: no MFMA.  Algorithmic traffic per chunk: N bytes read + transformed bytes written.
 //
 // One translation unit, cut along its stages, each header included here once in dependency order: zstd_enc_dev.h (what every stage
-// uses), zstd_enc_parse.h (source window, match_block, fast_block), zstd_enc_huf.h (huf_buildCTable), zstd_enc_entropy.h (FSE coder, bit
+// uses), zstd_enc_parse.h (source window, match_block, fast_block), zstd_enc_devparse.h (device_block: the lane-parallel parse of
+// TSX_ZSTD_PROFILE_DEVICE), zstd_enc_huf.h (huf_buildCTable), zstd_enc_entropy.h (FSE coder, bit
 // packer, literal and sequence stages).  This file keeps the pre-splitters, the frame loop, the GCM / CRC fusion, the kernels, the host side.
 #include "zstd_common.h"
 #include "gcm_dev.h"
@@ -41,6 +42,7 @@
 #include "xxh64_dev.h"
 #include "zstd_enc_dev.h"
 #include "zstd_enc_parse.h"
+#include "zstd_enc_devparse.h"
 #include "zstd_enc_huf.h"
 #include "zstd_enc_entropy.h"
 
@@ -297,7 +299,10 @@ __device__ __forceinline__ static bool zstd_compress_chunk(EncLds& L, const uint
         if (blockSize >= 7) {
             uint32_t rep[3] = {repc[0], repc[1], repc[2]};
             MfState ms;
-            if (fast) fast_block(src, ipos, blockSize, hashLong, cp, dictLimit, rep, seqs, ms, L.p.ring, lane);
+            // (the device profile has no levels, so `fast` is false with it: naming the profile in the first test as well is what keeps this
+            // kernel's register allocation and spill counts the ones it had with two parsers - profiles/device_profile_resource_usage.txt)
+            if (fast && profile != TSX_ZSTD_PROFILE_DEVICE) fast_block(src, ipos, blockSize, hashLong, cp, dictLimit, rep, seqs, ms, L.p.ring, lane);
+            else if (profile == TSX_ZSTD_PROFILE_DEVICE) device_block(src, srcSize, ipos, blockSize, hashLong, hashSmall, cp, rep, seqs, ms, lane);
             else match_block(src, srcSize, ipos, blockSize, hashLong, hashSmall, cp, dictLimit, rep, seqs, ms, L.p.ring, L.p.scr, lane, sched);
             stage_sync();
             gather_literals(lit, src, seqs, ms.nbSeq, ms.anchor, ms.lastLL, lane);

@@ -462,6 +462,8 @@ GpuTransformChunkEnumeration::GpuTransformChunkEnumeration(std::shared_ptr<Backe
       recordsValidate_(recordsValidate) {
     if (!inner_) throw std::invalid_argument("inner cannot be null");
     if (level_ < 0 || level_ > 3) throw std::invalid_argument("zstd level must be 1, 2 or 3 (0 = library default), " + std::to_string(level_) + " given");
+    if (profile_ > TSX_ZSTD_PROFILE_DEVICE) throw std::invalid_argument("unknown zstd profile " + std::to_string(profile_));
+    if (profile_ == TSX_ZSTD_PROFILE_DEVICE && level_ != 0) throw std::invalid_argument("the device zstd profile has no levels, " + std::to_string(level_) + " given");
     if (checksum_ && !compress_) throw std::invalid_argument("zstd checksum needs compression");
     if (verify_ && !compress_) throw std::invalid_argument("zstd verification needs compression");
     if (gcmVerify_ && !enc_) throw std::invalid_argument("GCM verification needs encryption");

@@ -253,6 +253,7 @@ public:
     // Zstandard level of the frames (compression.zstd.level): 0 = the library default (3, what the reference uses), 1, 2 or 3;
     // anything else is refused here, not at the first batch
     int zstdLevel() const { return level_; }
+    uint32_t zstdProfile() const { return profile_; }       // TSX_ZSTD_PROFILE_*; TSX_ZSTD_PROFILE_DEVICE takes no level (refused at construction)
     // content checksum in every frame (compression.zstd.checksum, TSX_ZSTD_CHECKSUM): off = the reference's bytes; refused here when
     // the chain does not compress.  (Every fetch verifies a checksum that is there - the fetch side has no option.)
     bool zstdChecksum() const { return checksum_; }
@@ -350,6 +351,7 @@ public:
     std::shared_ptr<ChunkIndex> chunkIndex();              // "Chunk index was not built, was finisher used?" until the object has been drained
     const std::vector<uint32_t>& crc32cOfOriginalChunks() const { return crcs_; }
     int zstdLevel() const { return inner_->zstdLevel(); }   // the enumeration's (the finisher transforms through it)
+    uint32_t zstdProfile() const { return inner_->zstdProfile(); }
     bool zstdChecksum() const { return inner_->zstdChecksum(); }
     bool zstdVerify() const { return inner_->zstdVerify(); }
     bool gcmVerify() const { return inner_->gcmVerify(); }

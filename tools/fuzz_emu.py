@@ -7,6 +7,9 @@ launches) must match the oracle chain.  Test infrastructure only (uses oracle/ a
     python tools/fuzz_emu.py --seconds 3000 --seed 1 --out /tmp/fuzz1.log
 With --level 1 or 2 (strategy fast): frames against libzstd at that level and the decoder, on inputs from all of tests/fuzz_cases.py's
 generators - structured, collision-rich, accelerated, and (the "big" ones, sized from the level's window) straddling and structured.
+With --device-profile (TSX_ZSTD_PROFILE_DEVICE: standard frames, no library's bytes): nothing is compared byte for byte; every frame goes
+through tests/device_profile_cases.check_frame (real libzstd and the inspector restore the chunk, offsets and blocks keep the format's
+limits, the frame is within ZSTD_compressBound), both emulated decoder forms restore the batch, and the same batch twice gives the same bytes.
 """
 import argparse
 import os
@@ -38,6 +41,7 @@ def main():
     ap.add_argument("--batches", type=int, default=0, help="stop after this many batches (0: when --seconds are over): the same cases on two builds")
     ap.add_argument("--out", default="")
     ap.add_argument("--level", type=int, choices=(1, 2, 3), default=3)
+    ap.add_argument("--device-profile", action="store_true", help="TSX_ZSTD_PROFILE_DEVICE: round trips through real libzstd instead of byte comparisons")
     ap.add_argument("--guests", action="store_true", help="fuzz the guest waves' hand-back instead: every launch's first workgroup sits on the reserved CU and is "
                                                           "made to give its chunk back at a random block; the full chain must still equal the oracle's")
     args = ap.parse_args()
@@ -49,6 +53,8 @@ def main():
     rng = np.random.default_rng(args.seed)
     t0 = time.time(); n_cases = 0; n_bytes = 0; bad = 0
     log = open(args.out, "a") if args.out else sys.stdout
+    if args.device_profile:
+        return fuzz_device_profile(args, emu, o, rng, log)
     if args.guests:
         return fuzz_guests(args, emu, o, rng, log)
     if args.level != 3:
@@ -112,6 +118,35 @@ def fuzz_fast(args, emu, o, rng, log):
         if batches % 10 == 0:
             print("[%6.0fs] level %d seed %d: %d cases, %.1f MB, %d bad" % (time.time() - t0, level, args.seed, n_cases, n_bytes / 1e6, bad), file=log, flush=True)
     print("DONE level %d seed %d: %d cases, %.1f MB, %d bad" % (level, args.seed, n_cases, n_bytes / 1e6, bad), file=log, flush=True)
+
+
+def fuzz_device_profile(args, emu, o, rng, log):
+    from tests import device_profile_cases as dc
+    t0 = time.time(); n_cases = 0; n_bytes = 0; bad = 0; batches = 0
+    while more(args, t0, batches):
+        kinds = ["gen", "collision", "accel", "gen", "gen", "big"]
+        cases = [gen_case(rng) if k == "gen" else level_case(rng, 1, k) for k in (kinds[int(rng.integers(0, len(kinds)))] for _ in range(args.batch))]
+        outs, d = dc.run(emu, nat.COMPRESS, cases)
+        again, d1 = dc.run(emu, nat.COMPRESS, cases)
+        for i, c in enumerate(cases):
+            try:
+                assert d["status"][i] == 0 and d1["status"][i] == 0, "status %d / %d" % (d["status"][i], d1["status"][i])
+                assert outs[i] == again[i], "the same chunk gave two frames"
+                dc.check_frame(o, outs[i], c, "case %d" % (n_cases + i))
+            except (AssertionError, ValueError, RuntimeError) as e:
+                bad += 1
+                path = "/tmp/fuzz_device_profile_bad_%d_%d.bin" % (args.seed, n_cases + i)
+                c.tofile(path)
+                print("DEVICE PROFILE MISMATCH seed %d case %d size %d: %s -> %s" % (args.seed, n_cases + i, c.size, e, path), file=log, flush=True)
+        try:
+            dc.check_decoders(emu, cases, outs)
+        except AssertionError as e:
+            bad += 1
+            print("DEVICE PROFILE DECODE MISMATCH seed %d case %d: %s" % (args.seed, n_cases, e), file=log, flush=True)
+        batches += 1; n_cases += len(cases); n_bytes += sum(int(c.size) for c in cases)
+        if batches % 10 == 0:
+            print("[%6.0fs] device profile seed %d: %d cases, %.1f MB, %d bad" % (time.time() - t0, args.seed, n_cases, n_bytes / 1e6, bad), file=log, flush=True)
+    print("DONE device profile seed %d: %d cases, %.1f MB, %d bad" % (args.seed, n_cases, n_bytes / 1e6, bad), file=log, flush=True)
 
 
 def fuzz_guests(args, emu, o, rng, log):

@@ -17,8 +17,13 @@ batches cross chunk boundaries wherever they fall), level 3, --callers contexts.
 and counters of the last 256-chunk batch (tsx_records_info.ms, repaired_chunks, batches) and, next to them, the separate-stage CRC
 kernels' crc_ms over the same bytes (tsx_crc32c_batch): what streaming those bytes through a CRC costs.  Default --out:
 profiles/records_level_bench.jsonl.
+--device-profile: TSX_ZSTD_PROFILE_DEVICE (standard frames from the lane-parallel parse, no library's bytes) against the exact level 3 of
+profile 1.5.7 in the same process: 1.5.7 / device / device / 1.5.7 per content.  Two regimes: the `value` shape (the defaults: 5 callers,
+8 x 1 GiB) and a lone segment (--callers 1 --segments 1: one 256-chunk batch at a time).  Every row carries GiB/s, frames / original and
+the service's kernel time; the exact rows' sample is compared with libzstd's frames, the device rows' sample is opened with the oracle's
+GCM and DECODED by libzstd.  Default --out: profiles/device_profile_level_bench.jsonl.
   python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8] [--levels 3] [--checksum] [--verify]
-                              [--verify-gcm] [--records] [--out FILE]"""
+                              [--verify-gcm] [--records] [--device-profile] [--out FILE]"""
 import argparse
 import ctypes
 import json
@@ -127,8 +132,11 @@ def main():
     ap.add_argument("--verify", action="store_true", help="each level without and with TSX_VERIFY, alternating")
     ap.add_argument("--verify-gcm", action="store_true", help="each level without and with TSX_VERIFY_GCM, alternating")
     ap.add_argument("--records", action="store_true", help="TSX_VALIDATE_RECORDS off / on / on / off on one valid segment of content B")
+    ap.add_argument("--device-profile", action="store_true", help="profile 1.5.7 level 3 / device / device / 1.5.7 in one process")
     ap.add_argument("--out", default=None, help="append every JSON line to this file as well")
     args = ap.parse_args()
+    if args.device_profile and not args.out:
+        args.out = os.path.join(ROOT, "profiles", "device_profile_level_bench.jsonl")
     if args.records and not args.out:
         args.out = os.path.join(ROOT, "profiles", "records_level_bench.jsonl")
     if args.verify_gcm and not args.out:
@@ -154,8 +162,11 @@ def main():
     n = args.segments * cps
     T = args.callers
     flags = nat.COMPRESS | nat.ENCRYPT | nat.CRC
-    levels = [(int(x), ck, vf, gv) for x in args.levels.split(",") for ck in ((False, True) if args.checksum else (False,))
+    levels = [(int(x), ck, vf, gv, nat.ZSTD_PROFILE_1_5_7) for x in args.levels.split(",") for ck in ((False, True) if args.checksum else (False,))
               for vf in ((False, True) if args.verify else (False,)) for gv in ((False, True) if args.verify_gcm else (False,))]
+    if args.device_profile:
+        exact, device = (3, False, False, False, nat.ZSTD_PROFILE_1_5_7), (0, False, False, False, nat.ZSTD_PROFILE_DEVICE)
+        levels, args.rounds = [exact, device, device, exact], 1
 
     def libzstd_frame(raw, level, checksum):
         """libzstd's frame as oracle/zstd_ref.c makes it, with ZSTD_c_checksumFlag on request."""
@@ -213,8 +224,9 @@ def main():
         order = []
         for r in range(args.rounds):
             order += levels if r % 2 == 0 else levels[::-1]
-        for level, ck, vf, gv in order:
-            p = nat.Native.make_params(flags | (nat.ZSTD_CHECKSUM if ck else 0) | (nat.VERIFY if vf else 0) | (nat.VERIFY_GCM if gv else 0), synth.KEY, synth.AAD, zstd_level=level)
+        for level, ck, vf, gv, profile in order:
+            p = nat.Native.make_params(flags | (nat.ZSTD_CHECKSUM if ck else 0) | (nat.VERIFY if vf else 0) | (nat.VERIFY_GCM if gv else 0), synth.KEY, synth.AAD, zstd_level=level,
+                                       zstd_profile=profile)
             ds = [d.copy() for _ in range(T)]
 
             def step(t):
@@ -244,16 +256,30 @@ def main():
             for i in sample:
                 got = host[i * slot:i * slot + int(ds[0]["dst_len"][i])].cpu().numpy().tobytes()
                 raw = np.ascontiguousarray(host_chunk(i)).tobytes()
+                if profile == nat.ZSTD_PROFILE_DEVICE:                  # no library's bytes: libzstd has to restore the chunk from the frame
+                    ok = ok and o.zstd_decompress_chunk(o.gcm_decrypt_chunk(synth.KEY, synth.AAD, got)) == raw
+                    continue
                 exp = o.gcm_encrypt_chunk(synth.KEY, ds[0]["iv"][i].tobytes(), synth.AAD, libzstd_frame(raw, level, ck))
                 ok = ok and got == exp
             tm = N.ctx_timing(ctxs[0])
-            row = {"content": content, "level": level, "checksum": ck, "verify": vf, "verify_gcm": gv, "gcm_ms": round(tm.gcm_ms, 2), "gcm_launches": tm.gcm_launches, "unzstd_ms": round(tm.unzstd_ms, 2), "unzstd_launches": tm.unzstd_launches, "gibs": round(args.steps * n * CH / GiB / el, 3), "elapsed_s": round(el, 3),
+            row = {"content": content, "profile": "device" if profile == nat.ZSTD_PROFILE_DEVICE else "1.5.7", "level": level, "checksum": ck, "verify": vf, "verify_gcm": gv, "gcm_ms": round(tm.gcm_ms, 2), "gcm_launches": tm.gcm_launches, "unzstd_ms": round(tm.unzstd_ms, 2), "unzstd_launches": tm.unzstd_launches, "gibs": round(args.steps * n * CH / GiB / el, 3), "elapsed_s": round(el, 3),
                    "ratio": round(float(ds[0]["dst_len"].astype(np.int64).sum() - 28 * n) / (n * CH), 4),
                    "kernel_ms": round(s1["kernel_ms"] - s0["kernel_ms"], 1), "launches": s1["launches"] - s0["launches"],
                    "chunks": n, "distinct_chunks": distinct, "steps": args.steps, "callers": T,
                    "checked_chunks": len(sample), "exact_vs_libzstd": bool(ok), "generated_in_s": round(gen_s, 1)}
+            if profile == nat.ZSTD_PROFILE_DEVICE:
+                row["decoded_by_libzstd"] = row.pop("exact_vs_libzstd")
             rows.append(row)
             emit(row)
+    if args.device_profile:
+        by = {}
+        for r in rows:
+            by.setdefault("%s_%s" % (r["content"], r["profile"]), []).append(r)
+        emit({"metric": "GiB/s of original bytes, profile 1.5.7 level 3 / device / device / 1.5.7 (runs in order)", "callers": T, "segments": args.segments,
+              "runs": {k: [r["gibs"] for r in v] for k, v in by.items()}, "ratio": {k: v[0]["ratio"] for k, v in by.items()},
+              "kernel_ms": {k: [r["kernel_ms"] for r in v] for k, v in by.items()},
+              "all_ok": all(r.get("exact_vs_libzstd", r.get("decoded_by_libzstd")) for r in rows), "libzstd": o.zstd_version(), "tsxform": N.version()})
+        return
     summary = {}
     for r in rows:
         k = "%s_L%d%s%s%s" % (r["content"], r["level"], "_checksum" if r["checksum"] else "", "_verify" if r["verify"] else "", "_verify_gcm" if r["verify_gcm"] else "")
