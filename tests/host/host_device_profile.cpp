@@ -2,18 +2,7 @@
 // libtsxform build given on the command line.  The profile's frames are no library's bytes: the enumeration's and the finisher's are
 // compared with the synchronous path's (tsx_transform_batch through the Backend, one chunk per call), and the oracle's libzstd restores
 // every chunk from its frame.  A level together with the profile, and an unknown profile, are refused at construction.
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-
-#include "tsxhost.hpp"
-
-extern "C" long long orc_zstd_decompress_chunk(const uint8_t* frame, size_t len, uint8_t* dst, size_t cap);   // oracle/zstd_ref.c
-extern "C" size_t orc_zstd_compress_chunk(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, int level);
-
-using namespace tsx;
-static int g_failed = 0;
-#define CHECK(c) do { if (!(c)) { printf("  FAIL line %d: %s\n", __LINE__, #c); g_failed++; } } while (0)
+#include "host_check.hpp"
 
 static Bytes libzstdRestores(const Bytes& frame, size_t n) {
     Bytes out(n + 16);
@@ -28,7 +17,7 @@ static Bytes syncFrame(Backend& be, const Bytes& part) {
     std::vector<tsx_chunk_desc> d(1);
     memset(d.data(), 0, sizeof(tsx_chunk_desc));
     d[0].src_len = (uint32_t)part.size(); d[0].dst_cap = (uint32_t)be.transformedBound(part.size(), TSX_COMPRESS);
-    Bytes src(((part.size() + 15) & ~(size_t)15) + 16), dst(((size_t)d[0].dst_cap + 15 & ~(size_t)15) + 16);
+    Bytes src(((part.size() + 15) & ~(size_t)15) + 16), dst((((size_t)d[0].dst_cap + 15) & ~(size_t)15) + 16);
     memcpy(src.data(), part.data(), part.size());
     tsx_batch_params p; memset(&p, 0, sizeof p);
     p.flags = TSX_COMPRESS; p.zstd_profile = TSX_ZSTD_PROFILE_DEVICE;
@@ -39,25 +28,14 @@ static Bytes syncFrame(Backend& be, const Bytes& part) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { printf("usage: host_device_profile <libtsxform path>\n"); return 2; }
-    auto be = std::make_shared<Backend>(argv[1]);
-    Bytes data(300000);
-    {   // log-like text: words of a small vocabulary picked by an LCG
-        static const char* words[] = {"offset=", "key=", "value=", "ts=", "partition ", "topic-a ", "topic-b ", "\n", "1700000", "abc", "xyz", "42 "};
-        uint32_t x = 4321; size_t i = 0;
-        while (i < data.size()) {
-            x = x * 1103515245u + 12345u;
-            const char* w = words[(x >> 16) % 12];
-            for (size_t k = 0; w[k] && i < data.size(); k++) data[i++] = (uint8_t)w[k];
-            if (((x >> 8) & 7) == 0 && i < data.size()) data[i++] = (uint8_t)('0' + ((x >> 20) % 10));
-        }
-    }
+    auto be = host_backend(argc, argv, "host_device_profile");
+    if (!be) return 2;
+    const Bytes data = host_log_text(300000, 4321);
     const int chunk = 140000;                                           // two blocks per chunk; 3 chunks, the last one short
     Bytes want;
     size_t level3 = 0;
     for (bool readAhead : {false, true}) {
-        auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(data), chunk);
-        auto g = std::make_shared<GpuTransformChunkEnumeration>(be, base, true, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_DEVICE, readAhead, 0);
+        auto g = std::make_shared<GpuTransformChunkEnumeration>(be, host_chunks(data, chunk), true, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_DEVICE, readAhead, 0);
         CHECK(g->zstdProfile() == TSX_ZSTD_PROFILE_DEVICE && g->zstdLevel() == 0);
         size_t off = 0, n = 0;
         Bytes all;
@@ -74,8 +52,7 @@ int main(int argc, char** argv) {
         if (!readAhead) want = all; else CHECK(all == want);
     }
     {   // the finisher transforms through the enumeration: its object is the profile's frames back to back; verify on upload accepts them
-        auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(data), chunk);
-        auto g = std::make_shared<GpuTransformChunkEnumeration>(be, base, true, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_DEVICE, false, 0, false, true);
+        auto g = std::make_shared<GpuTransformChunkEnumeration>(be, host_chunks(data, chunk), true, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_DEVICE, false, 0, false, true);
         GpuTransformFinisher fin(g, (int)data.size());
         CHECK(fin.zstdProfile() == TSX_ZSTD_PROFILE_DEVICE);
         Bytes object(1 << 20);
@@ -84,29 +61,14 @@ int main(int argc, char** argv) {
         printf("  device profile: %zu bytes (level 3: %zu, original %zu)\n", object.size(), level3, data.size());
     }
     {   // ... and so does the plain TransformFinisher over the enumeration
-        auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(data), chunk);
-        auto g = std::make_shared<GpuTransformChunkEnumeration>(be, base, true, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_DEVICE, false, 0);
+        auto g = std::make_shared<GpuTransformChunkEnumeration>(be, host_chunks(data, chunk), true, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_DEVICE, false, 0);
         TransformFinisher fin(g, (int)data.size());
         Bytes object;
         while (fin.hasMoreElements()) { const Bytes part = fin.nextElement(); object.insert(object.end(), part.begin(), part.end()); }
         CHECK(object == want);
     }
-    for (int level : {1, 2, 3}) {
-        bool threw = false;
-        try {
-            auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(data), chunk);
-            GpuTransformChunkEnumeration g(be, base, true, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_DEVICE, false, level);
-        } catch (const std::invalid_argument&) { threw = true; }
-        CHECK(threw);
-    }
-    {
-        bool threw = false;
-        try {
-            auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(data), chunk);
-            GpuTransformChunkEnumeration g(be, base, true, std::nullopt, secureRandomIvSupplier(), 2, false, 3u, false, 0);
-        } catch (const std::invalid_argument&) { threw = true; }
-        CHECK(threw);
-    }
-    printf("host device profile: %d failed\n", g_failed);
-    return g_failed ? 1 : 0;
+    for (int level : {1, 2, 3})
+        CHECK(host_throws<std::invalid_argument>([&] { GpuTransformChunkEnumeration g(be, host_chunks(data, chunk), true, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_DEVICE, false, level); }));
+    CHECK(host_throws<std::invalid_argument>([&] { GpuTransformChunkEnumeration g(be, host_chunks(data, chunk), true, std::nullopt, secureRandomIvSupplier(), 2, false, 3u, false, 0); }));
+    return host_done("host device profile");
 }

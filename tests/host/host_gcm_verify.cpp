@@ -2,46 +2,22 @@
 // gcmVerify) over a libtsxform build given on the command line.  That the option reaches the batch is shown by what only a verifying
 // batch does: with the library's test switch verify_damage_out_chunk set (one bit of a delivered chunk's tag), the chunk fails with
 // TSX_E_VERIFY - and raises what any failed chunk raises - exactly when the option is on; without it the damaged chunk is handed on.
-#include <dlfcn.h>
-
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-
-#include "tsxhost.hpp"
-
-using namespace tsx;
-static int g_failed = 0;
-#define CHECK(c) do { if (!(c)) { printf("  FAIL line %d: %s\n", __LINE__, #c); g_failed++; } } while (0)
+#include "host_check.hpp"
 
 int main(int argc, char** argv) {
-    if (argc < 2) { printf("usage: host_gcm_verify <libtsxform path>\n"); return 2; }
-    auto be = std::make_shared<Backend>(argv[1]);
-    void* h = dlopen(argv[1], RTLD_NOW | RTLD_LOCAL);                   // (the library the backend has loaded: same handle)
-    auto config = h ? (long long (*)(const char*, long long))dlsym(h, "tsx_debug_config") : nullptr;
-    if (!config) { printf("no tsx_debug_config in %s\n", argv[1]); return 2; }
-    Bytes data(120000);
-    {   // log-like text: words of a small vocabulary picked by an LCG
-        static const char* words[] = {"offset=", "key=", "value=", "ts=", "partition ", "topic-a ", "topic-b ", "\n", "1700000", "abc", "xyz", "42 "};
-        uint32_t x = 4242; size_t i = 0;
-        while (i < data.size()) {
-            x = x * 1103515245u + 12345u;
-            const char* w = words[(x >> 16) % 12];
-            for (size_t k = 0; w[k] && i < data.size(); k++) data[i++] = (uint8_t)w[k];
-            if (((x >> 8) & 7) == 0 && i < data.size()) data[i++] = (uint8_t)('0' + ((x >> 20) % 10));
-        }
-    }
-    DataKeyAndAAD keys;
-    keys.dataKey.resize(32); keys.aad.resize(32);
-    for (int i = 0; i < 32; i++) { keys.dataKey[i] = (uint8_t)(5 * i + 1); keys.aad[i] = (uint8_t)(99 + i); }
+    auto be = host_backend(argc, argv, "host_gcm_verify");
+    if (!be) return 2;
+    auto config = host_debug_config(argv[1]);
+    if (!config) return 2;
+    const Bytes data = host_log_text(120000, 4242);
+    const DataKeyAndAAD keys = host_keys();
     const int chunk = 40000;
     uint8_t counter = 0;
-    const IvSupplier fixedIvs = [&counter](uint8_t iv[12]) { for (int k = 0; k < 12; k++) iv[k] = (uint8_t)(counter + k); counter++; };
+    const IvSupplier fixedIvs = host_counting_ivs(counter);
     for (bool compress : {false, true}) {
         auto enumeration = [&](bool on, bool readAhead) {
-            counter = 0;                                                // the same IVs for every enumeration: the same bytes, option on or off
-            auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(data), chunk);
-            return std::make_shared<GpuTransformChunkEnumeration>(be, base, compress, keys, fixedIvs, 3, false, TSX_ZSTD_PROFILE_1_5_7, readAhead, 0, false, false, on);
+            counter = 0;
+            return std::make_shared<GpuTransformChunkEnumeration>(be, host_chunks(data, chunk), compress, keys, fixedIvs, 3, false, TSX_ZSTD_PROFILE_1_5_7, readAhead, 0, false, false, on);
         };
         Bytes objects[2];
         for (bool on : {false, true}) {
@@ -84,15 +60,10 @@ int main(int argc, char** argv) {
         config("verify_damage_out_chunk", -1);
     }
     // refused when the chain does not encrypt; accepted with encryption
-    for (bool encrypt : {false, true}) {
-        bool threw = false;
-        try {
-            auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(data), chunk);
-            GpuTransformChunkEnumeration g(be, base, true, encrypt ? std::optional<DataKeyAndAAD>(keys) : std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_1_5_7, false, 0,
+    for (bool encrypt : {false, true})
+        CHECK(host_throws<std::invalid_argument>([&] {
+            GpuTransformChunkEnumeration g(be, host_chunks(data, chunk), true, encrypt ? std::optional<DataKeyAndAAD>(keys) : std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_1_5_7, false, 0,
                                            false, false, true);
-        } catch (const std::invalid_argument&) { threw = true; }
-        CHECK(threw == !encrypt);
-    }
-    printf("host gcm verify: %d failed\n", g_failed);
-    return g_failed ? 1 : 0;
+        }) == !encrypt);
+    return host_done("host gcm verify");
 }

@@ -3,51 +3,29 @@
 // encrypting and the compressing chain: clean, the object is the same with the option on or off; with one bit of a batch's crc field
 // flipped, the option raises what any failed chunk raises (TSX_E_RECORDS' text) and without it the segment is handed on; a segment that
 // does not fit one batch is refused with the option on, never validated in part.
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-
-#include "tsxhost.hpp"
-
-using namespace tsx;
-static int g_failed = 0;
-#define CHECK(c) do { if (!(c)) { printf("  FAIL line %d: %s\n", __LINE__, #c); g_failed++; } } while (0)
-
-static uint32_t crc32cBitwise(const uint8_t* p, size_t n) {
-    uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < n; i++) { c ^= p[i]; for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u))); }
-    return ~c;
-}
-static void be32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
-static void appendBatch(Bytes& s, uint32_t total, uint32_t baseOffset) {
-    const size_t at = s.size();
-    s.resize(at + total, 0);
-    uint8_t* p = s.data() + at;
-    be32(p + 4, baseOffset); be32(p + 8, total - 12); p[16] = 2; be32(p + 57, 1);
-    for (uint32_t i = 61; i < total; i++) p[i] = (uint8_t)("partition topic-a offset=42 value=abc\n"[(i * 5 + baseOffset) % 38]);
-    be32(p + 17, crc32cBitwise(p + 21, total - 21));
-}
+#include "host_check.hpp"
 
 int main(int argc, char** argv) {
-    if (argc < 2) { printf("usage: host_records <libtsxform path>\n"); return 2; }
-    auto be = std::make_shared<Backend>(argv[1]);
+    auto be = host_backend(argc, argv, "host_records");
+    if (!be) return 2;
     Bytes data;
     std::vector<size_t> starts;
     const uint32_t lens[] = {900, 25000, 61, 47000, 3000, 33039};      // 109000 bytes: batch 3 runs from chunk 0 into chunk 2 (40000-byte chunks)
-    for (uint32_t i = 0; i < 6; i++) { starts.push_back(data.size()); appendBatch(data, lens[i], i); }
+    for (uint32_t i = 0; i < 6; i++) {
+        starts.push_back(data.size());
+        data.resize(data.size() + lens[i]);
+        harness_record_batch(data.data() + starts[i], lens[i], i, "partition topic-a offset=42 value=abc\n", 5);
+    }
     CHECK(data.size() == 109000);
-    DataKeyAndAAD keys;
-    keys.dataKey.resize(32); keys.aad.resize(32);
-    for (int i = 0; i < 32; i++) { keys.dataKey[i] = (uint8_t)(5 * i + 1); keys.aad[i] = (uint8_t)(99 + i); }
+    const DataKeyAndAAD keys = host_keys();
     const int chunk = 40000;
     uint8_t counter = 0;
-    const IvSupplier fixedIvs = [&counter](uint8_t iv[12]) { for (int k = 0; k < 12; k++) iv[k] = (uint8_t)(counter + k); counter++; };
+    const IvSupplier fixedIvs = host_counting_ivs(counter);
     const char* const names[3] = {"plain", "encrypt", "compress + encrypt"};
     for (int chain = 0; chain < 3; chain++) {
         auto enumeration = [&](const Bytes& segment, bool on, int batchChunks) {
-            counter = 0;                                                // the same IVs for every enumeration: the same bytes, option on or off
-            auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(segment), chunk);
-            return std::make_shared<GpuTransformChunkEnumeration>(be, base, chain == 2, chain ? std::optional<DataKeyAndAAD>(keys) : std::nullopt, fixedIvs, batchChunks, false,
+            counter = 0;
+            return std::make_shared<GpuTransformChunkEnumeration>(be, host_chunks(segment, chunk), chain == 2, chain ? std::optional<DataKeyAndAAD>(keys) : std::nullopt, fixedIvs, batchChunks, false,
                                                                   TSX_ZSTD_PROFILE_1_5_7, false, 0, false, false, false, on);
         };
         Bytes objects[2];
@@ -104,6 +82,5 @@ int main(int argc, char** argv) {
             if (chain == 0) printf("  segment of three chunks in batches of two, records validate %s: %s\n", on ? "on" : "off", what.empty() ? "no error" : "refused");
         }
     }
-    printf("host records: %d failed\n", g_failed);
-    return g_failed ? 1 : 0;
+    return host_done("host records");
 }

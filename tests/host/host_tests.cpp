@@ -14,6 +14,7 @@
 #include <string>
 
 #include "../../tiered-storage-for-apache-kafka_amd/host/tsxhost.hpp"
+#include "../harness_util.h"                                  // the oracle's zstd prototypes
 
 extern "C" {
 uint32_t orc_crc32c(const uint8_t* p, size_t n);
@@ -21,7 +22,6 @@ long orc_gcm_decrypt_chunk(const uint8_t key[32], const uint8_t* aad, size_t aad
 size_t orc_transform_chunk(unsigned flags, const uint8_t key[32], const uint8_t* aad, size_t aad_len, const uint8_t iv[12], const uint8_t* src, size_t n,
                            uint8_t* dst, size_t cap, uint8_t* scratch, uint32_t* crc_out);
 size_t orc_chain_bound(size_t n, unsigned flags);
-const char* orc_zstd_version(void);
 }
 
 using namespace tsx;

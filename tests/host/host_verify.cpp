@@ -2,39 +2,17 @@
 // zstdVerify) over a libtsxform build given on the command line.  That the option reaches the batch is shown by what only a verifying
 // batch does: with the library's test switch verify_damage_src_chunk set, a chunk fails with TSX_E_VERIFY - and raises what any failed
 // chunk raises - exactly when the option is on.
-#include <dlfcn.h>
-
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-
-#include "tsxhost.hpp"
-
-using namespace tsx;
-static int g_failed = 0;
-#define CHECK(c) do { if (!(c)) { printf("  FAIL line %d: %s\n", __LINE__, #c); g_failed++; } } while (0)
+#include "host_check.hpp"
 
 int main(int argc, char** argv) {
-    if (argc < 2) { printf("usage: host_verify <libtsxform path>\n"); return 2; }
-    auto be = std::make_shared<Backend>(argv[1]);
-    void* h = dlopen(argv[1], RTLD_NOW | RTLD_LOCAL);                   // (the library the backend has loaded: same handle)
-    auto config = h ? (long long (*)(const char*, long long))dlsym(h, "tsx_debug_config") : nullptr;
-    if (!config) { printf("no tsx_debug_config in %s\n", argv[1]); return 2; }
-    Bytes data(120000);
-    {   // log-like text: words of a small vocabulary picked by an LCG
-        static const char* words[] = {"offset=", "key=", "value=", "ts=", "partition ", "topic-a ", "topic-b ", "\n", "1700000", "abc", "xyz", "42 "};
-        uint32_t x = 4242; size_t i = 0;
-        while (i < data.size()) {
-            x = x * 1103515245u + 12345u;
-            const char* w = words[(x >> 16) % 12];
-            for (size_t k = 0; w[k] && i < data.size(); k++) data[i++] = (uint8_t)w[k];
-            if (((x >> 8) & 7) == 0 && i < data.size()) data[i++] = (uint8_t)('0' + ((x >> 20) % 10));
-        }
-    }
+    auto be = host_backend(argc, argv, "host_verify");
+    if (!be) return 2;
+    auto config = host_debug_config(argv[1]);
+    if (!config) return 2;
+    const Bytes data = host_log_text(120000, 4242);
     const int chunk = 40000;
     auto enumeration = [&](bool on, bool readAhead) {
-        auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(data), chunk);
-        return std::make_shared<GpuTransformChunkEnumeration>(be, base, true, std::nullopt, secureRandomIvSupplier(), 3, false, TSX_ZSTD_PROFILE_1_5_7, readAhead, 0, true, on);
+        return std::make_shared<GpuTransformChunkEnumeration>(be, host_chunks(data, chunk), true, std::nullopt, secureRandomIvSupplier(), 3, false, TSX_ZSTD_PROFILE_1_5_7, readAhead, 0, true, on);
     };
     Bytes objects[2];
     for (bool on : {false, true}) {
@@ -75,14 +53,7 @@ int main(int argc, char** argv) {
     config("verify_damage_src_chunk", -1);
     CHECK(be->strerror(TSX_E_VERIFY).find("does not restore") != std::string::npos);
     // refused when the chain does not compress; accepted with compression
-    for (bool compress : {false, true}) {
-        bool threw = false;
-        try {
-            auto base = std::make_shared<BaseTransformChunkEnumeration>(std::make_shared<ByteArrayInputStream>(data), chunk);
-            GpuTransformChunkEnumeration g(be, base, compress, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_1_5_7, false, 0, false, true);
-        } catch (const std::invalid_argument&) { threw = true; }
-        CHECK(threw == !compress);
-    }
-    printf("host verify: %d failed\n", g_failed);
-    return g_failed ? 1 : 0;
+    for (bool compress : {false, true})
+        CHECK(host_throws<std::invalid_argument>([&] { GpuTransformChunkEnumeration g(be, host_chunks(data, chunk), compress, std::nullopt, secureRandomIvSupplier(), 2, false, TSX_ZSTD_PROFILE_1_5_7, false, 0, false, true); }) == !compress);
+    return host_done("host verify");
 }

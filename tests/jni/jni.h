@@ -1,5 +1,5 @@
 /* TEST HARNESS ONLY: a minimal stand-in for the JDK's <jni.h> so that java/jni/tsx_jni.c can be compiled and driven without a
- * JVM (this image has no JDK).  It declares just the JNI types and the JNIEnv functions the shim uses; tests/jni/jni_harness.c
+ * JVM (this image has no JDK).  It declares just the JNI types and the JNIEnv functions the shim uses; tests/jni/jni_fake.h
  * provides them.  The real build uses $JAVA_HOME/include/jni.h (see the header of tsx_jni.c). */
 #ifndef TSX_TEST_JNI_H
 #define TSX_TEST_JNI_H

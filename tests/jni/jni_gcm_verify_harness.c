@@ -1,76 +1,44 @@
-/* TEST HARNESS ONLY: TsxNative.VERIFY_GCM through the JNI shim (java/jni/tsx_jni.c passes `flags` on as they are) with a hand-made JNIEnv
- * (tests/jni/jni.h), as tests/jni/jni_verify_harness.c drives TsxNative.VERIFY.  Checks, encrypt-only and compress + encrypt, slot and
- * packed layouts: clean chunks come back TSX_OK with the bytes of a batch without the flag; with the library's test switch
- * verify_damage_out_chunk set (one bit of that chunk's delivered tag), the chunk is TSX_E_VERIFY exactly when the flag is in the batch (so
- * the flag arrives) and delivered - damaged - without it; the flag without TSX_ENCRYPT is refused; detransform ignores it. */
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+/* TEST HARNESS ONLY: TsxNative.VERIFY_GCM through the JNI shim (java/jni/tsx_jni.c passes `flags` on as they are).  Checks, encrypt-only
+ * and compress + encrypt, slot and packed layouts: clean chunks come back TSX_OK with the bytes of a batch without the flag; with the
+ * library's test switch verify_damage_out_chunk set (one bit of that chunk's delivered tag), the chunk is TSX_E_VERIFY exactly when the
+ * flag is in the batch (so the flag arrives) and delivered - damaged - without it; the flag without TSX_ENCRYPT is refused; detransform
+ * ignores it. */
+#include "jni_fake.h"
+#include "../harness_util.h"
 
-#include "jni.h"
-#include "tsxform.h"
-
-struct _jobject { void* addr; jlong cap; };
-static jsize f_len(JNIEnv* e, jbyteArray a) { (void)e; return (jsize)a->cap; }
-static void f_region(JNIEnv* e, jbyteArray a, jsize off, jsize n, jbyte* out) { (void)e; memcpy(out, (char*)a->addr + off, (size_t)n); }
-static void* f_addr(JNIEnv* e, jobject b) { (void)e; return b ? b->addr : NULL; }
-static jlong f_cap(JNIEnv* e, jobject b) { (void)e; return b ? b->cap : -1; }
-static jstring f_str(JNIEnv* e, const char* s) { (void)e; jobject o = malloc(sizeof *o); o->addr = strdup(s); o->cap = (jlong)strlen(s); return o; }
-static const struct JNINativeInterface_ kFns = {f_len, f_region, f_addr, f_cap, f_str};
-
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_init(JNIEnv*, jclass);
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(JNIEnv*, jclass, jint, jbyteArray, jbyteArray, jint, jobject, jint, jobject, jobject);
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(JNIEnv*, jclass, jint, jbyteArray, jbyteArray, jint, jint, jobject, jint, jobject, jobject);
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_detransformBatch(JNIEnv*, jclass, jint, jbyteArray, jbyteArray, jobject, jint, jobject, jobject);
-long long tsx_debug_config(const char* key, long long value);          /* test hook of the library, not in the header */
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "FAILED line %d: %s\n", __LINE__, #c); return 1; } } while (0)
 #define N 3
 int main(void) {
-    JNIEnv envp = &kFns; JNIEnv* env = &envp;
-    CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_init(env, NULL) >= 1);
+    JNI_ENV(env);
+    CHECK(NATIVE(init)(env, NULL) >= 1);
     CHECK(TSX_VERIFY_GCM == 0x80u && TSX_E_VERIFY == -10);
     const uint32_t sizes[N] = {1000, 65537, 30001};
     unsigned char key[32], aad[32];
     for (int i = 0; i < 32; i++) { key[i] = (unsigned char)(7 * i + 3); aad[i] = (unsigned char)(200 - i); }
-    struct _jobject jkey = {key, 32}, jaad = {aad, 32};
+    struct _jobject jkey = JBUF(key, 32), jaad = JBUF(aad, 32);
     for (int compress = 0; compress <= 1; compress++) {
         const uint32_t chain = TSX_ENCRYPT | (compress ? TSX_COMPRESS : 0u);
-        tsx_chunk_desc d[N]; memset(d, 0, sizeof d);
-        size_t so = 0, dof = 0;
+        tsx_chunk_desc d[N];
+        size_t so, dof;
+        harness_slots(d, sizes, N, chain | TSX_VERIFY_GCM, &so, &dof);
         for (int i = 0; i < N; i++) {
-            d[i].src_off = so; d[i].dst_off = dof; d[i].src_len = sizes[i]; d[i].dst_cap = (uint32_t)tsx_transformed_bound(sizes[i], chain | TSX_VERIFY_GCM);
             CHECK(d[i].dst_cap == tsx_transformed_bound(sizes[i], chain));
             for (int k = 0; k < 12; k++) d[i].iv[k] = (uint8_t)(16 * i + k + compress);
-            so += ((sizes[i] + 15) & ~15u) + 16; dof += ((d[i].dst_cap + 15) & ~15u) + 16;
         }
         unsigned char* src = calloc(so, 1); unsigned char* dst = calloc(dof, 1); unsigned char* packed = calloc(dof, 1); unsigned char* ref = calloc(dof, 1);
         unsigned char* back = calloc(so, 1);
-        {   /* log-like text: words of a small vocabulary picked by an LCG */
-            static const char* words[] = {"offset=", "key=", "value=", "ts=", "partition ", "topic-a ", "topic-b ", "\n", "1700000", "abc", "xyz", "42 "};
-            uint32_t x = 99; size_t i = 0;
-            while (i < so) {
-                x = x * 1103515245u + 12345u;
-                const char* w = words[(x >> 16) % 12];
-                for (size_t k = 0; w[k] && i < so; k++) src[i++] = (unsigned char)w[k];
-                if (((x >> 8) & 7) == 0 && i < so) src[i++] = (unsigned char)('0' + ((x >> 20) % 10));
-            }
-        }
-        struct _jobject jsrc = {src, (jlong)so}, jdst = {dst, (jlong)dof}, jpk = {packed, (jlong)dof}, jref = {ref, (jlong)dof}, jback = {back, (jlong)so};
+        harness_log_text(src, so, 99);
+        struct _jobject jsrc = JBUF(src, so), jdst = JBUF(dst, dof), jpk = JBUF(packed, dof), jref = JBUF(ref, dof), jback = JBUF(back, so);
         tsx_chunk_desc r[N]; memcpy(r, d, sizeof r);
-        struct _jobject jr = {r, sizeof r};
-        CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(env, NULL, (jint)chain, &jkey, &jaad, TSX_ZSTD_PROFILE_1_5_7, &jr, N, &jsrc, &jref) == 0);
+        CHECK(NATIVE(transformBatch)(env, NULL, (jint)chain, &jkey, &jaad, TSX_ZSTD_PROFILE_1_5_7, &JBUF(r, sizeof r), N, &jsrc, &jref) == 0);
         for (int i = 0; i < N; i++) CHECK(r[i].status == 0 && r[i].dst_len >= 28);
         for (int damaged = 0; damaged <= 1; damaged++) {
             tsx_debug_config("verify_damage_out_chunk", damaged ? 1 : -1); tsx_debug_config("verify_damage_out_off", (long long)r[1].dst_len - 1);   /* last tag byte */
             for (int on = 0; on <= 1; on++) {
                 const jint flags = (jint)(chain | (on ? TSX_VERIFY_GCM : 0u));
                 tsx_chunk_desc s[N]; memcpy(s, d, sizeof s);
-                struct _jobject js = {s, sizeof s};
-                CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(env, NULL, flags, &jkey, &jaad, TSX_ZSTD_PROFILE_1_5_7, &js, N, &jsrc, &jdst) == 0);
+                CHECK(NATIVE(transformBatch)(env, NULL, flags, &jkey, &jaad, TSX_ZSTD_PROFILE_1_5_7, &JBUF(s, sizeof s), N, &jsrc, &jdst) == 0);
                 tsx_chunk_desc p[N]; memcpy(p, d, sizeof p);
-                struct _jobject jp = {p, sizeof p};
-                CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(env, NULL, flags, &jkey, &jaad, TSX_ZSTD_PROFILE_1_5_7, 3, &jp, N, &jsrc, &jpk) == 0);
+                CHECK(NATIVE(transformBatchPackedLevel)(env, NULL, flags, &jkey, &jaad, TSX_ZSTD_PROFILE_1_5_7, 3, &JBUF(p, sizeof p), N, &jsrc, &jpk) == 0);
                 size_t at = 0;
                 for (int i = 0; i < N; i++) {
                     const int hit = damaged && i == 1, fails = hit && on;
@@ -89,19 +57,18 @@ int main(void) {
         tsx_debug_config("verify_damage_out_chunk", -1);
         /* back through the fetch side's native with the upload's flags word: the flag means nothing there */
         {
-            tsx_chunk_desc b[N]; memset(b, 0, sizeof b);
-            for (int i = 0; i < N; i++) { b[i].src_off = d[i].dst_off; b[i].src_len = r[i].dst_len; b[i].dst_off = d[i].src_off; b[i].dst_cap = sizes[i]; }
-            struct _jobject jb = {b, sizeof b};
-            CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_detransformBatch(env, NULL, (jint)(chain | TSX_VERIFY_GCM), &jkey, &jaad, &jb, N, &jref, &jback) == 0);
+            tsx_chunk_desc b[N];
+            harness_fetch_slots(b, d, r, N);
+            CHECK(NATIVE(detransformBatch)(env, NULL, (jint)(chain | TSX_VERIFY_GCM), &jkey, &jaad, &JBUF(b, sizeof b), N, &jref, &jback) == 0);
             for (int i = 0; i < N; i++) CHECK(b[i].status == 0 && b[i].dst_len == sizes[i] && memcmp(back + d[i].src_off, src + d[i].src_off, sizes[i]) == 0);
         }
         /* the flag without encryption is refused */
         {
             tsx_chunk_desc b[N]; memcpy(b, d, sizeof b);
-            struct _jobject jb = {b, sizeof b};
+            struct _jobject jb = JBUF(b, sizeof b);
             const jint bad = (jint)(TSX_VERIFY_GCM | (compress ? TSX_COMPRESS : TSX_CRC));
-            CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(env, NULL, bad, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, &jb, N, &jsrc, &jdst) == TSX_E_INVAL);
-            CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(env, NULL, bad, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, 1, &jb, N, &jsrc, &jpk) == TSX_E_INVAL);
+            CHECK(NATIVE(transformBatch)(env, NULL, bad, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, &jb, N, &jsrc, &jdst) == TSX_E_INVAL);
+            CHECK(NATIVE(transformBatchPackedLevel)(env, NULL, bad, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, 1, &jb, N, &jsrc, &jpk) == TSX_E_INVAL);
         }
         free(src); free(dst); free(packed); free(ref); free(back);
     }

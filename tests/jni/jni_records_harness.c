@@ -1,74 +1,41 @@
-/* TEST HARNESS ONLY: TsxNative.VALIDATE_RECORDS through the JNI shim (java/jni/tsx_jni.c passes `flags` on as they are) with a hand-made
- * JNIEnv (tests/jni/jni.h), as tests/jni/jni_gcm_verify_harness.c drives TsxNative.VERIFY_GCM.  Three chunks that are, in order, one stream
- * of five hand-made v2 record batches; plain, encrypt and compress + encrypt chains, slot and packed layouts: a clean stream comes back
- * TSX_OK with the bytes of a batch without the flag; with one bit of a batch's crc field flipped in the source, the chunk that batch
- * begins in and the chunks behind it are TSX_E_RECORDS exactly when the flag is in the batch (so the flag arrives); detransform ignores it. */
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+/* TEST HARNESS ONLY: TsxNative.VALIDATE_RECORDS through the JNI shim (java/jni/tsx_jni.c passes `flags` on as they are).  Three chunks that
+ * are, in order, one stream of five hand-made v2 record batches; plain, encrypt and compress + encrypt chains, slot and packed layouts: a
+ * clean stream comes back TSX_OK with the bytes of a batch without the flag; with one bit of a batch's crc field flipped in the source, the
+ * chunk that batch begins in and the chunks behind it are TSX_E_RECORDS exactly when the flag is in the batch (so the flag arrives);
+ * detransform ignores it. */
+#include "jni_fake.h"
+#include "../harness_util.h"
 
-#include "jni.h"
-#include "tsxform.h"
-
-struct _jobject { void* addr; jlong cap; };
-static jsize f_len(JNIEnv* e, jbyteArray a) { (void)e; return (jsize)a->cap; }
-static void f_region(JNIEnv* e, jbyteArray a, jsize off, jsize n, jbyte* out) { (void)e; memcpy(out, (char*)a->addr + off, (size_t)n); }
-static void* f_addr(JNIEnv* e, jobject b) { (void)e; return b ? b->addr : NULL; }
-static jlong f_cap(JNIEnv* e, jobject b) { (void)e; return b ? b->cap : -1; }
-static jstring f_str(JNIEnv* e, const char* s) { (void)e; jobject o = malloc(sizeof *o); o->addr = strdup(s); o->cap = (jlong)strlen(s); return o; }
-static const struct JNINativeInterface_ kFns = {f_len, f_region, f_addr, f_cap, f_str};
-
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_init(JNIEnv*, jclass);
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(JNIEnv*, jclass, jint, jbyteArray, jbyteArray, jint, jobject, jint, jobject, jobject);
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(JNIEnv*, jclass, jint, jbyteArray, jbyteArray, jint, jint, jobject, jint, jobject, jobject);
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_detransformBatch(JNIEnv*, jclass, jint, jbyteArray, jbyteArray, jobject, jint, jobject, jobject);
-
-static uint32_t crc32c(const unsigned char* p, size_t n) {
-    uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < n; i++) { c ^= p[i]; for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u))); }
-    return ~c;
-}
-static void be32(unsigned char* p, uint32_t v) { p[0] = (unsigned char)(v >> 24); p[1] = (unsigned char)(v >> 16); p[2] = (unsigned char)(v >> 8); p[3] = (unsigned char)v; }
-/* one v2 record batch of `total` bytes at p: header, then text */
-static void make_batch(unsigned char* p, uint32_t total, uint32_t base_offset) {
-    memset(p, 0, 61);
-    be32(p + 4, base_offset); be32(p + 8, total - 12); p[16] = 2; be32(p + 57, 1);
-    for (uint32_t i = 61; i < total; i++) p[i] = (unsigned char)("offset=key=value=ts=\n"[(i * 7 + base_offset) % 21]);
-    be32(p + 17, crc32c(p + 21, total - 21));
-}
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "FAILED line %d: %s\n", __LINE__, #c); return 1; } } while (0)
 #define N 3
 #define BATCHES 5
 int main(void) {
-    JNIEnv envp = &kFns; JNIEnv* env = &envp;
-    CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_init(env, NULL) >= 1);
+    JNI_ENV(env);
+    CHECK(NATIVE(init)(env, NULL) >= 1);
     CHECK(TSX_VALIDATE_RECORDS == 0x100u && TSX_E_RECORDS == -11);
     const uint32_t blen[BATCHES] = {700, 30000, 61, 52000, 18239};           /* 101000 bytes; batch 3 begins in chunk 0 and ends in chunk 2 */
     const uint32_t sizes[N] = {40000, 40001, 20999};
     unsigned char* stream = malloc(101000);
     uint32_t bat[BATCHES], at0 = 0;
-    for (int b = 0; b < BATCHES; b++) { bat[b] = at0; make_batch(stream + at0, blen[b], (uint32_t)b); at0 += blen[b]; }
+    for (int b = 0; b < BATCHES; b++) { bat[b] = at0; harness_record_batch(stream + at0, blen[b], (uint32_t)b, "offset=key=value=ts=\n", 7); at0 += blen[b]; }
     CHECK(at0 == 101000 && bat[3] < 40000 && bat[4] > 80001);
     unsigned char key[32], aad[32];
     for (int i = 0; i < 32; i++) { key[i] = (unsigned char)(7 * i + 3); aad[i] = (unsigned char)(200 - i); }
-    struct _jobject jkey = {key, 32}, jaad = {aad, 32};
+    struct _jobject jkey = JBUF(key, 32), jaad = JBUF(aad, 32);
     const uint32_t chains[3] = {0u, TSX_ENCRYPT, TSX_ENCRYPT | TSX_COMPRESS};
     const char* const names[3] = {"plain", "encrypt", "compress + encrypt"};
     for (int c = 0; c < 3; c++) {
         const uint32_t chain = chains[c];
-        tsx_chunk_desc d[N]; memset(d, 0, sizeof d);
-        size_t so = 0, dof = 0;
+        tsx_chunk_desc d[N];
+        size_t so, dof;
+        harness_slots(d, sizes, N, chain | TSX_VALIDATE_RECORDS, &so, &dof);
         for (int i = 0; i < N; i++) {
-            d[i].src_off = so; d[i].dst_off = dof; d[i].src_len = sizes[i]; d[i].dst_cap = (uint32_t)tsx_transformed_bound(sizes[i], chain | TSX_VALIDATE_RECORDS);
             CHECK(d[i].dst_cap == tsx_transformed_bound(sizes[i], chain));
             for (int k = 0; k < 12; k++) d[i].iv[k] = (uint8_t)(16 * i + k + c);
-            so += ((sizes[i] + 15) & ~15u) + 16; dof += ((d[i].dst_cap + 15) & ~15u) + 16;
         }
         unsigned char* src = malloc(so); unsigned char* dst = calloc(dof, 1); unsigned char* packed = calloc(dof, 1); unsigned char* ref = calloc(dof, 1);
         unsigned char* back = calloc(so, 1);
         memset(src, 0x5A, so);                                                  /* the gaps between the slots are no part of the stream */
-        struct _jobject jsrc = {src, (jlong)so}, jdst = {dst, (jlong)dof}, jpk = {packed, (jlong)dof}, jref = {ref, (jlong)dof}, jback = {back, (jlong)so};
+        struct _jobject jsrc = JBUF(src, so), jdst = JBUF(dst, dof), jpk = JBUF(packed, dof), jref = JBUF(ref, dof), jback = JBUF(back, so);
         struct _jobject* const jk = chain & TSX_ENCRYPT ? &jkey : NULL; struct _jobject* const ja = chain & TSX_ENCRYPT ? &jaad : NULL;
         tsx_chunk_desc r[N];
         for (int damaged = 0; damaged <= 1; damaged++) {
@@ -85,18 +52,15 @@ int main(void) {
                 }
                 if (!damaged) {
                     memcpy(r, d, sizeof r);
-                    struct _jobject jr = {r, sizeof r};
-                    CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(env, NULL, (jint)chain, jk, ja, TSX_ZSTD_PROFILE_1_5_7, &jr, N, &jsrc, &jref) == 0);
+                    CHECK(NATIVE(transformBatch)(env, NULL, (jint)chain, jk, ja, TSX_ZSTD_PROFILE_1_5_7, &JBUF(r, sizeof r), N, &jsrc, &jref) == 0);
                     for (int k = 0; k < N; k++) CHECK(r[k].status == 0 && r[k].dst_len > 0);
                 }
                 for (int on = 0; on <= 1; on++) {
                     const jint flags = (jint)(chain | (on ? TSX_VALIDATE_RECORDS : 0u));
                     tsx_chunk_desc s[N]; memcpy(s, d, sizeof s);
-                    struct _jobject js = {s, sizeof s};
-                    CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(env, NULL, flags, jk, ja, TSX_ZSTD_PROFILE_1_5_7, &js, N, &jsrc, &jdst) == 0);
+                    CHECK(NATIVE(transformBatch)(env, NULL, flags, jk, ja, TSX_ZSTD_PROFILE_1_5_7, &JBUF(s, sizeof s), N, &jsrc, &jdst) == 0);
                     tsx_chunk_desc p[N]; memcpy(p, d, sizeof p);
-                    struct _jobject jp = {p, sizeof p};
-                    CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(env, NULL, flags, jk, ja, TSX_ZSTD_PROFILE_1_5_7, 3, &jp, N, &jsrc, &jpk) == 0);
+                    CHECK(NATIVE(transformBatchPackedLevel)(env, NULL, flags, jk, ja, TSX_ZSTD_PROFILE_1_5_7, 3, &JBUF(p, sizeof p), N, &jsrc, &jpk) == 0);
                     size_t pat = 0;
                     for (int k = 0; k < N; k++) {
                         const int fails = on && k >= first_bad;
@@ -113,10 +77,9 @@ int main(void) {
         }
         /* back through the fetch side's native with the upload's flags word: the flag means nothing there */
         {
-            tsx_chunk_desc b[N]; memset(b, 0, sizeof b);
-            for (int i = 0; i < N; i++) { b[i].src_off = d[i].dst_off; b[i].src_len = r[i].dst_len; b[i].dst_off = d[i].src_off; b[i].dst_cap = sizes[i]; }
-            struct _jobject jb = {b, sizeof b};
-            CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_detransformBatch(env, NULL, (jint)(chain | TSX_VALIDATE_RECORDS), jk, ja, &jb, N, &jref, &jback) == 0);
+            tsx_chunk_desc b[N];
+            harness_fetch_slots(b, d, r, N);
+            CHECK(NATIVE(detransformBatch)(env, NULL, (jint)(chain | TSX_VALIDATE_RECORDS), jk, ja, &JBUF(b, sizeof b), N, &jref, &jback) == 0);
             uint32_t at = 0;
             for (int i = 0; i < N; i++) { CHECK(b[i].status == 0 && b[i].dst_len == sizes[i] && memcmp(back + d[i].src_off, stream + at, sizes[i]) == 0); at += sizes[i]; }
         }

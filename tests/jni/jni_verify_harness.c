@@ -1,68 +1,34 @@
-/* TEST HARNESS ONLY: TsxNative.VERIFY through the JNI shim (java/jni/tsx_jni.c passes `flags` on as they are) with a hand-made JNIEnv
- * (tests/jni/jni.h), as tests/jni/jni_checksum_harness.c drives the checksum flag.  Checks: clean chunks come back TSX_OK with the bytes
- * of a batch without the flag, slot and packed layouts alike; with the library's test switch verify_damage_src_chunk set, that chunk is
- * TSX_E_VERIFY exactly when the flag is in the batch (so the flag arrives); the flag without TSX_COMPRESS is refused; detransform ignores it. */
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+/* TEST HARNESS ONLY: TsxNative.VERIFY through the JNI shim (java/jni/tsx_jni.c passes `flags` on as they are).  Checks: clean chunks come
+ * back TSX_OK with the bytes of a batch without the flag, slot and packed layouts alike; with the library's test switch
+ * verify_damage_src_chunk set, that chunk is TSX_E_VERIFY exactly when the flag is in the batch (so the flag arrives); the flag without
+ * TSX_COMPRESS is refused; detransform ignores it. */
+#include "jni_fake.h"
+#include "../harness_util.h"
 
-#include "jni.h"
-#include "tsxform.h"
-
-struct _jobject { void* addr; jlong cap; };
-static jsize f_len(JNIEnv* e, jbyteArray a) { (void)e; return (jsize)a->cap; }
-static void f_region(JNIEnv* e, jbyteArray a, jsize off, jsize n, jbyte* out) { (void)e; memcpy(out, (char*)a->addr + off, (size_t)n); }
-static void* f_addr(JNIEnv* e, jobject b) { (void)e; return b ? b->addr : NULL; }
-static jlong f_cap(JNIEnv* e, jobject b) { (void)e; return b ? b->cap : -1; }
-static jstring f_str(JNIEnv* e, const char* s) { (void)e; jobject o = malloc(sizeof *o); o->addr = strdup(s); o->cap = (jlong)strlen(s); return o; }
-static const struct JNINativeInterface_ kFns = {f_len, f_region, f_addr, f_cap, f_str};
-
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_init(JNIEnv*, jclass);
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(JNIEnv*, jclass, jint, jbyteArray, jbyteArray, jint, jobject, jint, jobject, jobject);
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(JNIEnv*, jclass, jint, jbyteArray, jbyteArray, jint, jint, jobject, jint, jobject, jobject);
-jint Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_detransformBatch(JNIEnv*, jclass, jint, jbyteArray, jbyteArray, jobject, jint, jobject, jobject);
-long long tsx_debug_config(const char* key, long long value);          /* test hook of the library, not in the header */
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "FAILED line %d: %s\n", __LINE__, #c); return 1; } } while (0)
 #define N 3
 int main(void) {
-    JNIEnv envp = &kFns; JNIEnv* env = &envp;
-    CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_init(env, NULL) >= 1);
+    JNI_ENV(env);
+    CHECK(NATIVE(init)(env, NULL) >= 1);
     CHECK(TSX_VERIFY == 0x20u && TSX_E_VERIFY == -10);
     const uint32_t sizes[N] = {1000, 30001, 60000};
-    tsx_chunk_desc d[N]; memset(d, 0, sizeof d);
-    size_t so = 0, dof = 0;
-    for (int i = 0; i < N; i++) {
-        d[i].src_off = so; d[i].dst_off = dof; d[i].src_len = sizes[i]; d[i].dst_cap = (uint32_t)tsx_transformed_bound(sizes[i], TSX_COMPRESS | TSX_VERIFY);
-        CHECK(d[i].dst_cap == tsx_transformed_bound(sizes[i], TSX_COMPRESS));
-        so += ((sizes[i] + 15) & ~15u) + 16; dof += ((d[i].dst_cap + 15) & ~15u) + 16;
-    }
+    tsx_chunk_desc d[N];
+    size_t so, dof;
+    harness_slots(d, sizes, N, TSX_COMPRESS | TSX_VERIFY, &so, &dof);
+    for (int i = 0; i < N; i++) CHECK(d[i].dst_cap == tsx_transformed_bound(sizes[i], TSX_COMPRESS));
     unsigned char* src = calloc(so, 1); unsigned char* dst = calloc(dof, 1); unsigned char* packed = calloc(dof, 1); unsigned char* ref = calloc(dof, 1);
     unsigned char* back = calloc(so, 1);
-    {   /* log-like text: words of a small vocabulary picked by an LCG */
-        static const char* words[] = {"offset=", "key=", "value=", "ts=", "partition ", "topic-a ", "topic-b ", "\n", "1700000", "abc", "xyz", "42 "};
-        uint32_t x = 99; size_t i = 0;
-        while (i < so) {
-            x = x * 1103515245u + 12345u;
-            const char* w = words[(x >> 16) % 12];
-            for (size_t k = 0; w[k] && i < so; k++) src[i++] = (unsigned char)w[k];
-            if (((x >> 8) & 7) == 0 && i < so) src[i++] = (unsigned char)('0' + ((x >> 20) % 10));
-        }
-    }
-    struct _jobject jsrc = {src, (jlong)so}, jdst = {dst, (jlong)dof}, jpk = {packed, (jlong)dof}, jref = {ref, (jlong)dof}, jback = {back, (jlong)so};
+    harness_log_text(src, so, 99);
+    struct _jobject jsrc = JBUF(src, so), jdst = JBUF(dst, dof), jpk = JBUF(packed, dof), jref = JBUF(ref, dof), jback = JBUF(back, so);
     tsx_chunk_desc r[N]; memcpy(r, d, sizeof r);
-    struct _jobject jr = {r, sizeof r};
-    CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(env, NULL, (jint)TSX_COMPRESS, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, &jr, N, &jsrc, &jref) == 0);
+    CHECK(NATIVE(transformBatch)(env, NULL, (jint)TSX_COMPRESS, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, &JBUF(r, sizeof r), N, &jsrc, &jref) == 0);
     for (int damaged = 0; damaged <= 1; damaged++) {
         tsx_debug_config("verify_damage_src_chunk", damaged ? 1 : -1); tsx_debug_config("verify_damage_src_off", 12345);
         for (int on = 0; on <= 1; on++) {
             const jint flags = (jint)(TSX_COMPRESS | (on ? TSX_VERIFY : 0u));
             tsx_chunk_desc s[N]; memcpy(s, d, sizeof s);
-            struct _jobject js = {s, sizeof s};
-            CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(env, NULL, flags, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, &js, N, &jsrc, &jdst) == 0);
+            CHECK(NATIVE(transformBatch)(env, NULL, flags, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, &JBUF(s, sizeof s), N, &jsrc, &jdst) == 0);
             tsx_chunk_desc p[N]; memcpy(p, d, sizeof p);
-            struct _jobject jp = {p, sizeof p};
-            CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(env, NULL, flags, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, 3, &jp, N, &jsrc, &jpk) == 0);
+            CHECK(NATIVE(transformBatchPackedLevel)(env, NULL, flags, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, 3, &JBUF(p, sizeof p), N, &jsrc, &jpk) == 0);
             size_t at = 0;
             for (int i = 0; i < N; i++) {
                 const int fails = damaged && on && i == 1;
@@ -78,18 +44,17 @@ int main(void) {
     tsx_debug_config("verify_damage_src_chunk", -1);
     /* back through the fetch side's native with the upload's flags word: the flag means nothing there */
     {
-        tsx_chunk_desc b[N]; memset(b, 0, sizeof b);
-        for (int i = 0; i < N; i++) { b[i].src_off = d[i].dst_off; b[i].src_len = r[i].dst_len; b[i].dst_off = d[i].src_off; b[i].dst_cap = sizes[i]; }
-        struct _jobject jb = {b, sizeof b};
-        CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_detransformBatch(env, NULL, (jint)(TSX_COMPRESS | TSX_VERIFY), NULL, NULL, &jb, N, &jref, &jback) == 0);
+        tsx_chunk_desc b[N];
+        harness_fetch_slots(b, d, r, N);
+        CHECK(NATIVE(detransformBatch)(env, NULL, (jint)(TSX_COMPRESS | TSX_VERIFY), NULL, NULL, &JBUF(b, sizeof b), N, &jref, &jback) == 0);
         for (int i = 0; i < N; i++) CHECK(b[i].status == 0 && b[i].dst_len == sizes[i] && memcmp(back + d[i].src_off, src + d[i].src_off, sizes[i]) == 0);
     }
     /* the flag without compression is refused */
     {
         tsx_chunk_desc b[N]; memcpy(b, d, sizeof b);
-        struct _jobject jb = {b, sizeof b};
-        CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(env, NULL, (jint)TSX_VERIFY, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, &jb, N, &jsrc, &jdst) == TSX_E_INVAL);
-        CHECK(Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(env, NULL, (jint)(TSX_VERIFY | TSX_CRC), NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, 1, &jb, N, &jsrc, &jpk) == TSX_E_INVAL);
+        struct _jobject jb = JBUF(b, sizeof b);
+        CHECK(NATIVE(transformBatch)(env, NULL, (jint)TSX_VERIFY, NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, &jb, N, &jsrc, &jdst) == TSX_E_INVAL);
+        CHECK(NATIVE(transformBatchPackedLevel)(env, NULL, (jint)(TSX_VERIFY | TSX_CRC), NULL, NULL, TSX_ZSTD_PROFILE_1_5_7, 1, &jb, N, &jsrc, &jpk) == TSX_E_INVAL);
     }
     free(src); free(dst); free(packed); free(ref); free(back);
     printf("jni verify ok\n");

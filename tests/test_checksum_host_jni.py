@@ -1,14 +1,11 @@
 """The Zstandard content checksum through the host layers: the JNI shim (tests/jni/jni_checksum_harness.c: TsxNative.ZSTD_CHECKSUM in the
 flags it passes on) and the C++ host layer's option (tests/host/host_checksum.cpp: zstdChecksum, the twin of the Java classes'), over the
 CPU-emulated library here and the product library on a GPU box (-m gpu).  No JDK here: the Java classes are checked as source."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OBUILD = os.path.join(ROOT, "oracle", "_build")
+from tests import hostjni
 
 
 def _need157(oracle):
@@ -16,39 +13,15 @@ def _need157(oracle):
         pytest.skip("libzstd 1.5.7 not available")
 
 
-def _jni(libdir, libname, env_extra, tmp_path):
-    exe = str(tmp_path / ("jni_checksum_" + libname))
-    subprocess.check_call(["gcc", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "tests", "jni"), "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "java", "jni", "tsx_jni.c"), os.path.join(ROOT, "tests", "jni", "jni_checksum_harness.c"),
-                           "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-L" + OBUILD, "-loracle", "-Wl,-rpath," + OBUILD, "-ldl", "-o", exe])
-    r = subprocess.run([exe], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "jni checksum ok" in r.stdout, r.stdout + r.stderr
-    return r.stdout
-
-
-def _host(lib, env_extra, tmp_path):
-    exe = str(tmp_path / "host_checksum")
-    host = os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd", "host")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-I" + host, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "host", "host_checksum.cpp"), os.path.join(host, "tsxhost.cpp"),
-                           "-L" + OBUILD, "-loracle", "-Wl,-rpath," + OBUILD, "-ldl", "-lpthread", "-o", exe])
-    r = subprocess.run([exe, lib], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "host checksum: 0 failed" in r.stdout, r.stdout + r.stderr
-    return r.stdout
-
-
 def test_jni_flag_against_the_emulated_library(oracle, tmp_path):
     _need157(oracle)
-    from tests.emu import emu_native
-    lib = emu_native.build()
-    out = _jni(os.path.dirname(lib), "tsxform_emu", {"TSX_ALLOW_ANY_ARCH": "1"}, tmp_path)
+    out = hostjni.run_jni("jni_checksum_harness", hostjni.emu_target(), tmp_path, "jni checksum ok", libs=("-ldl",))
     assert "checksum on, level 1:" in out and "checksum off, level 0:" in out
 
 
 def test_host_option_against_the_emulated_library(oracle, tmp_path):
     _need157(oracle)
-    from tests.emu import emu_native
-    out = _host(emu_native.build(), {"TSX_ALLOW_ANY_ARCH": "1"}, tmp_path)
+    out = hostjni.run_host("host_checksum", hostjni.emu_target(), "host checksum: 0 failed")
     assert "checksum on:" in out and "checksum off:" in out
 
 
@@ -56,25 +29,20 @@ def test_java_classes_carry_the_option():
     """The constant equals the header's and the Python binding's; both upload-side classes take the option, refuse it without
     compression, and put the flag into the batch; the fetch-side classes have no such option (the frame decides)."""
     import tsxform
-    jdir = os.path.join(ROOT, "java", "io", "aiven", "kafka", "tieredstorage", "gpu")
-    h = open(os.path.join(ROOT, "include", "tsxform.h")).read()
-    c = int(re.search(r"#define\s+TSX_ZSTD_CHECKSUM\s+(0x[0-9A-Fa-f]+)u", h).group(1), 16)
-    j = int(re.search(r"public static final int ZSTD_CHECKSUM = (0x[0-9A-Fa-f]+);", open(os.path.join(jdir, "TsxNative.java")).read()).group(1), 16)
-    assert c == j == tsxform._native.ZSTD_CHECKSUM == 8
-    assert re.search(r"#define\s+TSX_ABI_VERSION\s+4\b", h)
-    for f in ("GpuTransformChunkEnumeration.java", "GpuTransformFinisher.java"):
-        code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(os.path.join(jdir, f)).read(), flags=re.S))
+    assert hostjni.header_define("TSX_ZSTD_CHECKSUM") == hostjni.java_constant("ZSTD_CHECKSUM") == tsxform._native.ZSTD_CHECKSUM == 8
+    assert hostjni.header_define("TSX_ABI_VERSION") == 4
+    for f in ("GpuTransformChunkEnumeration", "GpuTransformFinisher"):
+        code = hostjni.java_code(f)
         assert re.search(r"final int zstdLevel, final boolean zstdChecksum\)", code), f
         assert re.search(r"if \(zstdChecksum && !compress\) \{\s*throw new IllegalArgumentException\(", code), f
         assert re.search(r"\(zstdChecksum \? TsxNative\.ZSTD_CHECKSUM : 0\)", code), f
         assert re.search(r"readAhead, zstdLevel, false\);", code), f      # the older constructors: off, the reference's bytes
-    for f in ("GpuDetransformChunkEnumeration.java", "GpuChunkManager.java", "GpuChunkCache.java"):
-        assert "ZSTD_CHECKSUM" not in open(os.path.join(jdir, f)).read(), f
+    for f in ("GpuDetransformChunkEnumeration", "GpuChunkManager", "GpuChunkCache"):
+        assert "ZSTD_CHECKSUM" not in hostjni.java_text(f), f
 
 
 @pytest.mark.gpu
 def test_jni_and_host_checksum_against_the_product_library(gpu, oracle, tmp_path):
     _need157(oracle)
-    import tsxform
-    _jni(os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd"), "tsxform", {}, tmp_path)
-    _host(tsxform._native.LIB_PATH, {}, tmp_path)
+    hostjni.run_jni("jni_checksum_harness", hostjni.product_target(), tmp_path, "jni checksum ok", libs=("-ldl",))
+    hostjni.run_host("host_checksum", hostjni.product_target(), "host checksum: 0 failed")

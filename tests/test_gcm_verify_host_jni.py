@@ -1,33 +1,11 @@
 """Verify on upload, AES-GCM stage, through the host layers: the JNI shim (tests/jni/jni_gcm_verify_harness.c: TsxNative.VERIFY_GCM in the
 flags it passes on) and the C++ host layer's option (tests/host/host_gcm_verify.cpp: gcmVerify, the twin of the Java classes'), over the
 CPU-emulated library here and the product library on a GPU box (-m gpu).  No JDK here: the Java classes are checked as source."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _jni(libdir, libname, env_extra, tmp_path):
-    exe = str(tmp_path / ("jni_gcm_verify_" + libname))
-    subprocess.check_call(["gcc", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "tests", "jni"), "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "java", "jni", "tsx_jni.c"), os.path.join(ROOT, "tests", "jni", "jni_gcm_verify_harness.c"),
-                           "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-ldl", "-o", exe])
-    r = subprocess.run([exe], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "jni gcm verify ok" in r.stdout, r.stdout + r.stderr
-    return r.stdout
-
-
-def _host(lib, env_extra, tmp_path):
-    exe = str(tmp_path / "host_gcm_verify")
-    host = os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd", "host")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-I" + host, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "host", "host_gcm_verify.cpp"), os.path.join(host, "tsxhost.cpp"), "-ldl", "-lpthread", "-o", exe])
-    r = subprocess.run([exe, lib], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "host gcm verify: 0 failed" in r.stdout, r.stdout + r.stderr
-    return r.stdout
+from tests import hostjni
 
 
 def _check_jni_output(out):
@@ -44,14 +22,11 @@ def _check_host_output(out):
 
 
 def test_jni_flag_against_the_emulated_library(tmp_path):
-    from tests.emu import emu_native
-    lib = emu_native.build()
-    _check_jni_output(_jni(os.path.dirname(lib), "tsxform_emu", {"TSX_ALLOW_ANY_ARCH": "1"}, tmp_path))
+    _check_jni_output(hostjni.run_jni("jni_gcm_verify_harness", hostjni.emu_target(), tmp_path, "jni gcm verify ok", oracle=False, libs=("-ldl",)))
 
 
 def test_host_option_against_the_emulated_library(tmp_path):
-    from tests.emu import emu_native
-    _check_host_output(_host(emu_native.build(), {"TSX_ALLOW_ANY_ARCH": "1"}, tmp_path))
+    _check_host_output(hostjni.run_host("host_gcm_verify", hostjni.emu_target(), "host gcm verify: 0 failed"))
 
 
 def test_java_classes_carry_the_option():
@@ -59,29 +34,23 @@ def test_java_classes_carry_the_option():
     refuse it without encryption and put the flag into the batch; the overloads that were there delegate with false; the fetch side has
     no such option."""
     import tsxform
-    jdir = os.path.join(ROOT, "java", "io", "aiven", "kafka", "tieredstorage", "gpu")
-    h = open(os.path.join(ROOT, "include", "tsxform.h")).read()
-    jn = open(os.path.join(jdir, "TsxNative.java")).read()
-    c = int(re.search(r"#define\s+TSX_VERIFY_GCM\s+(0x[0-9A-Fa-f]+)u", h).group(1), 16)
-    j = int(re.search(r"public static final int VERIFY_GCM = (0x[0-9A-Fa-f]+);", jn).group(1), 16)
-    assert c == j == tsxform._native.VERIFY_GCM == 0x80
-    assert re.search(r"#define\s+TSX_ABI_VERSION\s+4\b", h)
-    for f in ("GpuTransformChunkEnumeration.java", "GpuTransformFinisher.java"):
-        code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(os.path.join(jdir, f)).read(), flags=re.S))
+    assert hostjni.header_define("TSX_VERIFY_GCM") == hostjni.java_constant("VERIFY_GCM") == tsxform._native.VERIFY_GCM == 0x80
+    assert hostjni.header_define("TSX_ABI_VERSION") == 4
+    for f in ("GpuTransformChunkEnumeration", "GpuTransformFinisher"):
+        code = hostjni.java_code(f)
         assert re.search(r"final boolean zstdVerify,\s*final boolean gcmVerify\)", code), f
         assert re.search(r"final boolean zstdChecksum,\s*final boolean zstdVerify\)", code), f      # the overload that was there stays
         assert re.search(r"if \(gcmVerify && keyAndAad == null\) \{\s*throw new IllegalArgumentException\(", code), f
         assert re.search(r"\(gcmVerify \? TsxNative\.VERIFY_GCM : 0\)", code), f
         assert re.search(r"zstdLevel,\s*zstdChecksum,\s*zstdVerify,\s*false\);", code), f       # ... and delegates: off
-    for f in ("GpuDetransformChunkEnumeration.java", "GpuChunkManager.java", "GpuChunkCache.java"):
-        src = open(os.path.join(jdir, f)).read()
+    for f in ("GpuDetransformChunkEnumeration", "GpuChunkManager", "GpuChunkCache"):
+        src = hostjni.java_text(f)
         assert "VERIFY" not in src and "gcmVerify" not in src, f
-    shim = open(os.path.join(ROOT, "java", "jni", "tsx_jni.c")).read()
+    shim = open(hostjni.SHIM).read()
     assert "p->flags = (uint32_t)flags;" in shim and "VERIFY" not in shim   # the flags word passes through untouched
 
 
 @pytest.mark.gpu
 def test_jni_and_host_gcm_verify_against_the_product_library(gpu, tmp_path):
-    import tsxform
-    _check_jni_output(_jni(os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd"), "tsxform", {}, tmp_path))
-    _check_host_output(_host(tsxform._native.LIB_PATH, {}, tmp_path))
+    _check_jni_output(hostjni.run_jni("jni_gcm_verify_harness", hostjni.product_target(), tmp_path, "jni gcm verify ok", oracle=False, libs=("-ldl",)))
+    _check_host_output(hostjni.run_host("host_gcm_verify", hostjni.product_target(), "host gcm verify: 0 failed"))

@@ -2,30 +2,18 @@
 image, so this is the evidence that the C half of the Java binding moves the right pointers - against the CPU-emulated library
 here, against the product library on a GPU box (-m gpu)."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "jni", "_build")
+from tests import hostjni
 
-
-def _build_and_run(libdir, libname, env_extra):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "jni_harness_" + libname)
-    subprocess.check_call(["gcc", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "tests", "jni"), "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "java", "jni", "tsx_jni.c"), os.path.join(ROOT, "tests", "jni", "jni_harness.c"),
-                           "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-o", exe])
-    r = subprocess.run([exe], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "jni shim ok" in r.stdout, r.stdout + r.stderr
+BUILD = os.path.join(hostjni.ROOT, "tests", "jni", "_build")
 
 
 def test_jni_shim_against_the_emulated_library():
-    from tests.emu import emu_native
-    lib = emu_native.build()
-    _build_and_run(os.path.dirname(lib), "tsxform_emu", {"TSX_ALLOW_ANY_ARCH": "1"})
+    hostjni.run_jni("jni_harness", hostjni.emu_target(), BUILD, "jni shim ok", oracle=False)
 
 
 @pytest.mark.gpu
 def test_jni_shim_against_the_product_library(gpu):
-    _build_and_run(os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd"), "tsxform", {})
+    hostjni.run_jni("jni_harness", hostjni.product_target(), BUILD, "jni shim ok", oracle=False)

@@ -1,50 +1,21 @@
 """Zstandard levels through the host layers: the JNI shim's level-taking natives (tests/jni/jni_levels_harness.c) and the C++ host layer's
 level option (tests/host/host_levels.cpp), over the CPU-emulated library here and the product library on a GPU box (-m gpu)."""
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OBUILD = os.path.join(ROOT, "oracle", "_build")
-
-
-def _jni(libdir, libname, env_extra, tmp_path):
-    exe = str(tmp_path / ("jni_levels_" + libname))
-    subprocess.check_call(["gcc", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "tests", "jni"), "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "java", "jni", "tsx_jni.c"), os.path.join(ROOT, "tests", "jni", "jni_levels_harness.c"),
-                           "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-L" + OBUILD, "-loracle", "-Wl,-rpath," + OBUILD, "-o", exe])
-    r = subprocess.run([exe], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "jni levels ok" in r.stdout, r.stdout + r.stderr
-    return r.stdout
-
-
-def _host(lib, env_extra, tmp_path):
-    exe = str(tmp_path / "host_levels")
-    host = os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd", "host")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-I" + host, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "host", "host_levels.cpp"), os.path.join(host, "tsxhost.cpp"),
-                           "-L" + OBUILD, "-loracle", "-Wl,-rpath," + OBUILD, "-ldl", "-lpthread", "-o", exe])
-    r = subprocess.run([exe, lib], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "host levels: 0 failed" in r.stdout, r.stdout + r.stderr
-    return r.stdout
+from tests import hostjni
 
 
 def test_jni_level_natives_against_the_emulated_library(oracle, tmp_path):
-    from tests.emu import emu_native
-    lib = emu_native.build()
-    out = _jni(os.path.dirname(lib), "tsxform_emu", {"TSX_ALLOW_ANY_ARCH": "1"}, tmp_path)
+    out = hostjni.run_jni("jni_levels_harness", hostjni.emu_target(), tmp_path, "jni levels ok")
     assert "level 1:" in out
 
 
 def test_host_level_option_against_the_emulated_library(oracle, tmp_path):
-    from tests.emu import emu_native
-    out = _host(emu_native.build(), {"TSX_ALLOW_ANY_ARCH": "1"}, tmp_path)
+    out = hostjni.run_host("host_levels", hostjni.emu_target(), "host levels: 0 failed")
     assert "level 2:" in out
 
 
 @pytest.mark.gpu
 def test_jni_and_host_levels_against_the_product_library(gpu, oracle, tmp_path):
-    import tsxform
-    _jni(os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd"), "tsxform", {}, tmp_path)
-    _host(tsxform._native.LIB_PATH, {}, tmp_path)
+    hostjni.run_jni("jni_levels_harness", hostjni.product_target(), tmp_path, "jni levels ok")
+    hostjni.run_host("host_levels", hostjni.product_target(), "host levels: 0 failed")

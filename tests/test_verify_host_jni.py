@@ -1,46 +1,21 @@
 """Verify on upload through the host layers: the JNI shim (tests/jni/jni_verify_harness.c: TsxNative.VERIFY in the flags it passes on)
 and the C++ host layer's option (tests/host/host_verify.cpp: zstdVerify, the twin of the Java classes'), over the CPU-emulated library
 here and the product library on a GPU box (-m gpu).  No JDK here: the Java classes are checked as source."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _jni(libdir, libname, env_extra, tmp_path):
-    exe = str(tmp_path / ("jni_verify_" + libname))
-    subprocess.check_call(["gcc", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "tests", "jni"), "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "java", "jni", "tsx_jni.c"), os.path.join(ROOT, "tests", "jni", "jni_verify_harness.c"),
-                           "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-ldl", "-o", exe])
-    r = subprocess.run([exe], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "jni verify ok" in r.stdout, r.stdout + r.stderr
-    return r.stdout
-
-
-def _host(lib, env_extra, tmp_path):
-    exe = str(tmp_path / "host_verify")
-    host = os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd", "host")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-I" + host, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "host", "host_verify.cpp"), os.path.join(host, "tsxhost.cpp"), "-ldl", "-lpthread", "-o", exe])
-    r = subprocess.run([exe, lib], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "host verify: 0 failed" in r.stdout, r.stdout + r.stderr
-    return r.stdout
+from tests import hostjni
 
 
 def test_jni_flag_against_the_emulated_library(tmp_path):
-    from tests.emu import emu_native
-    lib = emu_native.build()
-    out = _jni(os.path.dirname(lib), "tsxform_emu", {"TSX_ALLOW_ANY_ARCH": "1"}, tmp_path)
+    out = hostjni.run_jni("jni_verify_harness", hostjni.emu_target(), tmp_path, "jni verify ok", oracle=False, libs=("-ldl",))
     assert "verify on, source damaged: status 0 -10 0" in out and "verify off, source damaged: status 0 0 0" in out
     assert "verify on, source intact: status 0 0 0" in out
 
 
 def test_host_option_against_the_emulated_library(tmp_path):
-    from tests.emu import emu_native
-    out = _host(emu_native.build(), {"TSX_ALLOW_ANY_ARCH": "1"}, tmp_path)
+    out = hostjni.run_host("host_verify", hostjni.emu_target(), "host verify: 0 failed")
     assert "verify on:" in out and "verify off:" in out
     assert "damaged source, verify on: the frame written for this chunk does not restore it" in out and "damaged source, verify off: no error" in out
 
@@ -49,28 +24,20 @@ def test_java_classes_carry_the_option():
     """The constants equal the header's and the Python binding's; both upload-side classes have an overload that ends in the option,
     refuse it without compression and put the flag into the batch; the older constructors pass false; the fetch side has no such option."""
     import tsxform
-    jdir = os.path.join(ROOT, "java", "io", "aiven", "kafka", "tieredstorage", "gpu")
-    h = open(os.path.join(ROOT, "include", "tsxform.h")).read()
-    jn = open(os.path.join(jdir, "TsxNative.java")).read()
-    c = int(re.search(r"#define\s+TSX_VERIFY\s+(0x[0-9A-Fa-f]+)u", h).group(1), 16)
-    j = int(re.search(r"public static final int VERIFY = (0x[0-9A-Fa-f]+);", jn).group(1), 16)
-    assert c == j == tsxform._native.VERIFY == 0x20
-    ce = int(re.search(r"#define\s+TSX_E_VERIFY\s+(-\d+)", h).group(1))
-    je = int(re.search(r"public static final int E_VERIFY = (-\d+);", jn).group(1))
-    assert ce == je == tsxform._native.E_VERIFY == -10
-    assert re.search(r"#define\s+TSX_ABI_VERSION\s+4\b", h)
-    for f in ("GpuTransformChunkEnumeration.java", "GpuTransformFinisher.java"):
-        code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(os.path.join(jdir, f)).read(), flags=re.S))
+    assert hostjni.header_define("TSX_VERIFY") == hostjni.java_constant("VERIFY") == tsxform._native.VERIFY == 0x20
+    assert hostjni.header_define("TSX_E_VERIFY") == hostjni.java_constant("E_VERIFY") == tsxform._native.E_VERIFY == -10
+    assert hostjni.header_define("TSX_ABI_VERSION") == 4
+    for f in ("GpuTransformChunkEnumeration", "GpuTransformFinisher"):
+        code = hostjni.java_code(f)
         assert re.search(r"final boolean zstdChecksum,\s*final boolean zstdVerify\)", code), f
         assert re.search(r"if \(zstdVerify && !compress\) \{\s*throw new IllegalArgumentException\(", code), f
         assert re.search(r"\(zstdVerify \? TsxNative\.VERIFY : 0\)", code), f
         assert re.search(r"zstdLevel, zstdChecksum, false\);", code), f      # the older constructors: off
-    for f in ("GpuDetransformChunkEnumeration.java", "GpuChunkManager.java", "GpuChunkCache.java"):
-        assert "VERIFY" not in open(os.path.join(jdir, f)).read(), f
+    for f in ("GpuDetransformChunkEnumeration", "GpuChunkManager", "GpuChunkCache"):
+        assert "VERIFY" not in hostjni.java_text(f), f
 
 
 @pytest.mark.gpu
 def test_jni_and_host_verify_against_the_product_library(gpu, tmp_path):
-    import tsxform
-    _jni(os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd"), "tsxform", {}, tmp_path)
-    _host(tsxform._native.LIB_PATH, {}, tmp_path)
+    hostjni.run_jni("jni_verify_harness", hostjni.product_target(), tmp_path, "jni verify ok", oracle=False, libs=("-ldl",))
+    hostjni.run_host("host_verify", hostjni.product_target(), "host verify: 0 failed")
