@@ -14,12 +14,12 @@ CSRC = os.path.join(ROOT, "tiered-storage-for-apache-kafka_amd", "csrc")
 
 def test_no_access_of_the_parse_leaves_its_blocks(tmp_path):
     subprocess.check_call(["make", "-s", "-C", CSRC, "emu-asan-device-profile"], stdout=subprocess.DEVNULL)
-    names = dc.names()
+    names = dc.names() + dc.EDGE + dc.AIMED                             # (the second family's window-edge pairs and aimed block sequences too)
     path = tmp_path / "cases.bin"
     with open(path, "wb") as f:
         f.write(struct.pack("<I", len(names)))
         for n in names:
-            x = dc.case(n)
+            x = dc.fuzz_case(n) if n in dc.EDGE + dc.AIMED else dc.case(n)
             f.write(struct.pack("<I", int(x.size))); f.write(x.tobytes())
     exe = os.path.join(ROOT, "tests", "emu", "_build", "asan_device_profile")
     r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=1500, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0"))

@@ -10,6 +10,7 @@ generators - structured, collision-rich, accelerated, and (the "big" ones, sized
 With --device-profile (TSX_ZSTD_PROFILE_DEVICE: standard frames, no library's bytes): nothing is compared byte for byte; every frame goes
 through tests/device_profile_cases.check_frame (real libzstd and the inspector restore the chunk, offsets and blocks keep the format's
 limits, the frame is within ZSTD_compressBound), both emulated decoder forms restore the batch, and the same batch twice gives the same bytes.
+Its window-sized inputs are sized by the profile's own 2 MiB window, not by a level's.
 """
 import argparse
 import os
@@ -121,11 +122,27 @@ def fuzz_fast(args, emu, o, rng, log):
 
 
 def fuzz_device_profile(args, emu, o, rng, log):
+    """Mostly gen_case's default sizes and collision-rich or accelerated inputs of 300 - 420 KB; at a low rate (1 in 16 draws each) the inputs
+    sized by the profile's own 2 MiB window: a pair of blocks straddling its low edge, a structured input of 2 MiB + 0 .. 300 000 bytes, and
+    tests/device_profile_cases.edge_case with its two copies D apart, D drawn around 2 MiB (half of them within 2 bytes of it)."""
     from tests import device_profile_cases as dc
+    from tests.fuzz_cases import straddle_case
+
+    def draw(kind):
+        if kind == "gen":
+            return gen_case(rng)
+        if kind == "straddle":
+            return straddle_case(rng, dc.WINDOW)
+        if kind == "big":
+            return gen_case(rng, dc.WINDOW + int(rng.integers(0, 300001)))
+        if kind == "edge":
+            D = dc.WINDOW + int(rng.integers(-2, 3) if rng.integers(0, 2) else rng.integers(-5000, 5001))
+            return dc.edge_case(D, ("zeros", "noise")[int(rng.integers(0, 2))], key=int(rng.integers(0, 1 << 30)))
+        return level_case(rng, 3, kind)
     t0 = time.time(); n_cases = 0; n_bytes = 0; bad = 0; batches = 0
     while more(args, t0, batches):
-        kinds = ["gen", "collision", "accel", "gen", "gen", "big"]
-        cases = [gen_case(rng) if k == "gen" else level_case(rng, 1, k) for k in (kinds[int(rng.integers(0, len(kinds)))] for _ in range(args.batch))]
+        kinds = ["gen"] * 9 + ["collision"] * 2 + ["accel"] * 2 + ["straddle", "big", "edge"]
+        cases = [draw(kinds[int(rng.integers(0, len(kinds)))]) for _ in range(args.batch)]
         outs, d = dc.run(emu, nat.COMPRESS, cases)
         again, d1 = dc.run(emu, nat.COMPRESS, cases)
         for i, c in enumerate(cases):
