@@ -78,7 +78,7 @@ extern "C" {
 /* Modifier of a transform with any stage combination: validate the SOURCE as a Kafka log before it is uploaded.  The batch's chunks,
  * concatenated in descriptor order ([src_off, src_off + src_len) of chunk 0, 1, ...; gaps between slots are not part of it, chunks of
  * length 0 contribute nothing), are taken as ONE byte stream that begins on a record-batch boundary and ends on one - a whole segment in
- * one call; a segment split over several calls is out of scope.  Every batch of the stream is checked on the device the way
+ * one call; a segment split over several calls goes through tsx_transform_batch_stream below.  Every batch of the stream is checked on the device the way
  * DefaultRecordBatch.ensureValid() plus a walk over the log would check it (fields big-endian: baseOffset @0, batchLength @8,
  * partitionLeaderEpoch @12, magic @16, crc @17, attributes @21 ...):
  *   at least 61 bytes are left in the stream; batchLength >= 49 as a signed 32-bit value; position + 12 + batchLength <= the stream's
@@ -312,6 +312,50 @@ size_t tsx_transformed_bound(size_t n, uint32_t flags);
  * threads, README.md:218-222). */
 int tsx_transform_batch(tsx_ctx* ctx, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n,
                         const void* src, size_t src_size, void* dst, size_t dst_size, int mem_kind);
+
+/* ---- TSX_VALIDATE_RECORDS over several calls: a segment streamed in batches ---------------------
+ * The state of one stream between two calls: 192 bytes of plain memory that the CALLER owns - no pointers inside, it may be copied or
+ * moved, and it belongs to no context (consecutive calls may use different contexts, or the pool). */
+#define TSX_RECORDS_STATE_BYTES 192
+typedef struct tsx_records_state { uint64_t opaque[24]; } tsx_records_state;
+
+/* Begins a stream of stream_bytes bytes in all - the segment's size, which the broker knows (segmentSizeInBytes) before it reads the
+ * first chunk.  TSX_E_INVAL: st == NULL. */
+int tsx_records_begin(tsx_records_state* st, uint64_t stream_bytes);
+
+/* tsx_transform_batch in every respect - every mem_kind, ctx == NULL from the pool, every chain - except that the call's chunks CONTINUE
+ * the stream st describes instead of being a stream of their own.
+ *   - params->flags must contain TSX_VALIDATE_RECORDS, else TSX_E_INVAL.
+ *   - bytes consumed so far + the call's src_len sum > the declared length: TSX_E_INVAL before anything is touched.
+ *   - every number in the state is checked on entry (carried header bytes <= 60, consumed <= declared, the open batch's end <= declared,
+ *     ...): a state that was never begun, or a damaged one, is TSX_E_INVAL.  A length yields a verdict, never an address.
+ *   - on any negative return the state is as it was, bit for bit; a call with n == 0, or with only empty chunks, changes nothing.
+ * Same walk, same verdict: for every stream S and every cut of S into calls and chunks, tsx_records_result after the last call reports
+ * the batches, compressed_batches, first_bad_pos and first_bad_reason that ONE call over S would.  The declared length makes that
+ * possible: "fewer than 61 bytes left" and "the batch reaches beyond the stream's end" are decided against it, in ensureValid()'s order,
+ * as soon as a batch's 61 header bytes have arrived.
+ * Carried from call to call: a header whose first 61 bytes have not all arrived, raw (at most 60 bytes, over as many tiny calls as it
+ * takes); or a batch whose header has passed its checks and whose end lies behind the call's end - its position, the CRC field it expects,
+ * the bytes still to come and the raw CRC32C register over its bytes from offset 21 to the call's end.  Such an open batch may span
+ * several whole calls.
+ * Where the verdict lands: let d be the last byte the verdict needs - bad_pos itself for "fewer than 61 bytes left"; bad_pos + 60 for
+ * length, beyond-the-stream and magic; the batch's last byte for CRC.  The verdict falls in the call that holds byte d.  Earlier calls
+ * have been delivered TSX_OK (an all-or-nothing upload discards them).  In that call the chunk that holds stream position
+ * max(bad_pos, the call's first position) and every chunk behind it get TSX_E_RECORDS and dst_len 0; the chunks in front of it are
+ * delivered; a chunk that already carries another error keeps it.  Every LATER call on that state gets TSX_E_RECORDS on every chunk, with
+ * nothing allocated or launched.
+ * "No chunk is reported TSX_OK whose bytes the validator has not covered" holds in this sense: the bytes of an open batch are covered
+ * when the batch closes, and a stream whose tsx_records_result never reaches 1 has NOT been validated - the caller must ask.  When the
+ * validator finds no memory the call returns TSX_E_NOMEM (the state stays, the call may be repeated).
+ * A stream given in ONE call, with the declared length equal to the call's bytes, yields the statuses, bytes and info of
+ * tsx_transform_batch with the flag. */
+int tsx_transform_batch_stream(tsx_ctx* ctx, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n,
+                               const void* src, size_t src_size, void* dst, size_t dst_size, int mem_kind,
+                               tsx_records_state* st);
+
+/* 1: the stream is complete (the bytes consumed equal the declared length); 0: not yet; TSX_E_INVAL: a state that was never begun (or
+ * out == NULL).  In the 0 and 1 cases *out describes the stream so far: repaired_chunks summed over the calls, ms that of the last call. */
+int tsx_records_result(const tsx_records_state* st, tsx_records_info* out);
 
 /* Inverse chain: [verify tag + AES-256-GCM decrypt] -> [Zstd decode], CRC32C(restored).
  * Replaces DecryptionChunkEnumeration.nextElement + DecompressionChunkEnumeration.nextElement. */

@@ -125,6 +125,9 @@ public class GpuTransformFinisher {
     private final boolean zstdVerify;        // every frame is read back on the device and compared with its chunk
     private final boolean gcmVerify;         // every delivered IV || C || TAG is decrypted and authenticated on the device
     private final boolean recordsValidate;   // the source, as one stream, is walked on the device as a Kafka v2 log
+    private final long recordsStreamBytes;   // >= 0: the same walk over a segment of that many bytes, streamed in several batches; -1: off
+    private final ByteBuffer recordsState;   // ... the one stream state, passed with every batch (a tsx_records_state)
+    private long recordsConsumed;            // ... source bytes the batches so far have held
     private final int device;
     private final boolean readAhead;
     private final Bucket rateLimitingBucket;
@@ -226,8 +229,45 @@ public class GpuTransformFinisher {
                                 final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
                                 final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
                                 final boolean zstdVerify, final boolean gcmVerify, final boolean recordsValidate) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, originalFileSize,
+            chunkingEnabled, rateLimitingBucket, readAhead, zstdLevel, zstdChecksum, zstdVerify, gcmVerify, recordsValidate, -1);
+    }
+
+    /**
+     * @param recordsStreamBytes streamed validation of the source, plugin configuration key {@code segment.records.validate.streamed}
+     *                  (INTEGRATION.md 2): -1 = off (what every other constructor passes); 0 or more = the segment's size in bytes
+     *                  (remoteLogSegmentMetadata.segmentSizeInBytes()).  The same walk as {@code recordsValidate}, but the segment need not
+     *                  fit one batch: this object begins ONE stream state here and passes it with every batch - batches are issued one
+     *                  after another, read-ahead included.  A batch that crosses from one device call into the next is judged when its
+     *                  last byte arrives; a chunk that fails raises what any failed chunk raises, with the first invalid batch's
+     *                  position and reason in the text; when the source is exhausted the stream must be complete, else an
+     *                  IllegalStateException names the bytes consumed and the bytes declared.  Together with {@code recordsValidate}
+     *                  it is refused.
+     */
+    public GpuTransformFinisher(final TransformChunkEnumeration inner, final boolean compress, final DataKeyAndAAD keyAndAad,
+                                final int batchChunks, final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
+                                final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
+                                final boolean zstdVerify, final boolean gcmVerify, final boolean recordsValidate,
+                                final long recordsStreamBytes) {
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
         this.recordsValidate = recordsValidate;
+        if (recordsStreamBytes < -1) {
+            throw new IllegalArgumentException("recordsStreamBytes must be -1 (off) or the segment's size, " + recordsStreamBytes + " given");
+        }
+        if (recordsValidate && recordsStreamBytes >= 0) {
+            throw new IllegalArgumentException("segment.records.validate in one batch and streamed exclude each other");
+        }
+        this.recordsStreamBytes = recordsStreamBytes;
+        if (recordsStreamBytes >= 0) {
+            this.recordsState = ByteBuffer.allocateDirect(TsxNative.RECORDS_STATE_BYTES).order(java.nio.ByteOrder.LITTLE_ENDIAN);
+            final int began = TsxNative.recordsBegin(recordsState, recordsStreamBytes);
+            if (began != TsxNative.OK) {
+                throw new RuntimeException(TsxNative.strerror(began));
+            }
+        } else {
+            this.recordsState = null;
+        }
         if (zstdChecksum && !compress) {
             throw new IllegalArgumentException("Zstd checksum needs compression");
         }
@@ -289,7 +329,33 @@ public class GpuTransformFinisher {
             | (zstdChecksum ? TsxNative.ZSTD_CHECKSUM : 0)
             | (zstdVerify ? TsxNative.VERIFY : 0)
             | (gcmVerify ? TsxNative.VERIFY_GCM : 0)
-            | (recordsValidate ? TsxNative.VALIDATE_RECORDS : 0);
+            | (recordsValidate ? TsxNative.VALIDATE_RECORDS : 0)
+            | (recordsStreamBytes >= 0 ? TsxNative.VALIDATE_RECORDS : 0);
+    }
+
+    /** What a failed chunk raises: the code's text and, for a streamed validation's {@link TsxNative#E_RECORDS}, where and why. */
+    private String chunkError(final int status) {
+        final String what = TsxNative.strerror(status);
+        if (recordsStreamBytes < 0 || status != TsxNative.E_RECORDS) {
+            return what;
+        }
+        final ByteBuffer info = ByteBuffer.allocateDirect(TsxNative.RECORDS_INFO_BYTES).order(java.nio.ByteOrder.LITTLE_ENDIAN);
+        if (TsxNative.recordsResult(recordsState, info) < 0) {
+            return what;
+        }
+        final String[] why = {"none", "truncated", "length", "magic", "crc"};
+        final int reason = info.getInt(TsxNative.RECORDS_INFO_FIRST_BAD_REASON);
+        return what + " (first invalid record batch at stream position " + info.getLong(TsxNative.RECORDS_INFO_FIRST_BAD_POS)
+            + ", reason " + reason + " " + why[reason >= 0 && reason < why.length ? reason : 0] + ")";
+    }
+
+    /** The source is exhausted: a stream that is not complete has not been validated. */
+    private void requireStreamComplete() {
+        final ByteBuffer info = ByteBuffer.allocateDirect(TsxNative.RECORDS_INFO_BYTES).order(java.nio.ByteOrder.LITTLE_ENDIAN);
+        if (TsxNative.recordsResult(recordsState, info) != 1) {
+            throw new IllegalStateException("segment.records.validate.streamed: the segment ended at " + recordsConsumed + " bytes, "
+                + recordsStreamBytes + " were declared; it has not been validated");
+        }
     }
 
     private static long align16(final long v) {
@@ -422,6 +488,9 @@ public class GpuTransformFinisher {
             in.add(inner.nextElement());
         }
         if (in.isEmpty()) {
+            if (recordsStreamBytes >= 0) {
+                requireStreamComplete();
+            }
             return new PackedBatch(null, new int[0]);
         }
         if (recordsValidate && inner.hasMoreElements()) {
@@ -462,7 +531,10 @@ public class GpuTransformFinisher {
         final byte[] key = keyAndAad != null ? keyAndAad.dataKey.getEncoded() : null;   // a copy (SecretKeySpec.getEncoded clones)
         final int rc;
         try {
-            rc = zstdLevel == 0
+            rc = recordsStreamBytes >= 0
+                ? TsxNative.transformBatchPackedStream(flags, key, keyAndAad != null ? keyAndAad.aad : null, zstdProfile, zstdLevel,
+                    descs, in.size(), src, object, recordsState)
+                : zstdLevel == 0
                 ? TsxNative.transformBatchPacked(flags, key, keyAndAad != null ? keyAndAad.aad : null, zstdProfile, descs, in.size(), src, object)
                 : TsxNative.transformBatchPackedLevel(flags, key, keyAndAad != null ? keyAndAad.aad : null, zstdProfile, zstdLevel,
                     descs, in.size(), src, object);
@@ -476,6 +548,9 @@ public class GpuTransformFinisher {
             PinnedPool.release(object);
             throw new RuntimeException(TsxNative.strerror(rc));
         }
+        for (final byte[] chunk : in) {
+            recordsConsumed += chunk.length;
+        }
         final int[] sizes = new int[in.size()];
         long at = 0;
         for (int i = 0; i < in.size(); i++) {
@@ -483,7 +558,7 @@ public class GpuTransformFinisher {
             final int status = descs.getInt(base + TsxNative.DESC_STATUS);
             if (status != TsxNative.OK) {
                 PinnedPool.release(object);
-                throw new RuntimeException(TsxNative.strerror(status));   // as EncryptionChunkEnumeration.java:76-78
+                throw new RuntimeException(chunkError(status));   // as EncryptionChunkEnumeration.java:76-78
             }
             sizes[i] = descs.getInt(base + TsxNative.DESC_DST_LEN);
             if (descs.getLong(base + TsxNative.DESC_DST_OFF) != at) {

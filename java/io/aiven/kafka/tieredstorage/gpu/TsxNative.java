@@ -212,4 +212,34 @@ public final class TsxNative {
 
     public static native int detransformBatch(int flags, byte[] key, byte[] aad,
                                               ByteBuffer descs, int n, ByteBuffer src, ByteBuffer dst);
+
+    /** Size of a tsx_records_state (include/tsxform.h): the state of one segment that is validated over several batches. */
+    public static final int RECORDS_STATE_BYTES = 192;
+    /** Size of a tsx_records_info and where its fields lie (little-endian). */
+    public static final int RECORDS_INFO_BYTES = 40;
+    public static final int RECORDS_INFO_BATCHES = 0;
+    public static final int RECORDS_INFO_COMPRESSED_BATCHES = 8;
+    public static final int RECORDS_INFO_FIRST_BAD_POS = 16;
+    public static final int RECORDS_INFO_FIRST_BAD_REASON = 24;
+
+    /** tsx_records_begin: {@code state} describes a stream of {@code streamBytes} bytes in all (the segment's size) of which none has been seen. */
+    public static native int recordsBegin(ByteBuffer state, long streamBytes);
+
+    /**
+     * tsx_transform_batch_stream, slot layout and packed: {@link #transformBatchLevel} / {@link #transformBatchPackedLevel} whose chunks
+     * CONTINUE the stream {@code state} describes ({@code flags} must contain {@link #VALIDATE_RECORDS}).  The state is the caller's:
+     * consecutive batches may run on any thread, one after another.  A negative return leaves it as it was.
+     */
+    public static native int transformBatchStream(int flags, byte[] key, byte[] aad, int zstdProfile, int zstdLevel,
+                                                  ByteBuffer descs, int n, ByteBuffer src, ByteBuffer dst, ByteBuffer state);
+
+    public static native int transformBatchPackedStream(int flags, byte[] key, byte[] aad, int zstdProfile, int zstdLevel,
+                                                        ByteBuffer descs, int n, ByteBuffer src, ByteBuffer dst, ByteBuffer state);
+
+    /**
+     * tsx_records_result: 1 when the stream is complete (the bytes consumed equal the declared length), 0 when it is not, negative for a
+     * state that was never begun; {@code info} (a direct little-endian buffer of {@link #RECORDS_INFO_BYTES}) receives the tsx_records_info
+     * of the stream so far.
+     */
+    public static native int recordsResult(ByteBuffer state, ByteBuffer info);
 }

@@ -74,8 +74,9 @@ static int fill_params(JNIEnv* env, tsx_batch_params* p, jint flags, jbyteArray 
     return TSX_OK;
 }
 
+/* state: NULL, or the direct buffer that holds a tsx_records_state (a segment validated over several batches: the batch continues it) */
 static jint run(JNIEnv* env, int detransform, int mem_kind, jint flags, jbyteArray key, jbyteArray aad, jint profile, jint level,
-                jobject descs, jint n, jobject src, jobject dst) {
+                jobject descs, jint n, jobject src, jobject dst, jobject state) {
     tsx_batch_params p;
     int rc = fill_params(env, &p, flags, key, aad, profile, level);
     if (rc == TSX_OK) {
@@ -85,8 +86,14 @@ static jint run(JNIEnv* env, int detransform, int mem_kind, jint flags, jbyteArr
         const jlong cap = (*env)->GetDirectBufferCapacity(env, dst);
         const jlong scap = (*env)->GetDirectBufferCapacity(env, src);
         if (n < 0 || !d || !s || !o || (*env)->GetDirectBufferCapacity(env, descs) < (jlong)n * (jlong)sizeof(tsx_chunk_desc)) rc = TSX_E_INVAL;
+        tsx_records_state* st = NULL;
+        if (state) {
+            st = (tsx_records_state*)(*env)->GetDirectBufferAddress(env, state);
+            if (detransform || !st || (*env)->GetDirectBufferCapacity(env, state) < (jlong)sizeof(tsx_records_state)) rc = TSX_E_INVAL;
+        }
         /* the capacities of the two direct buffers are the bounds the library validates every descriptor against (ABI 3) */
-        if (rc == TSX_OK)
+        if (rc == TSX_OK && st) rc = tsx_transform_batch_stream(NULL, &p, d, (uint32_t)n, s, (size_t)scap, o, (size_t)cap, mem_kind, st);
+        else if (rc == TSX_OK)
             rc = detransform ? tsx_detransform_batch(NULL, &p, d, (uint32_t)n, s, (size_t)scap, o, (size_t)cap, mem_kind)
                              : tsx_transform_batch(NULL, &p, d, (uint32_t)n, s, (size_t)scap, o, (size_t)cap, mem_kind);
     }
@@ -97,31 +104,62 @@ static jint run(JNIEnv* env, int detransform, int mem_kind, jint flags, jbyteArr
 JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatch(
     JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jobject descs, jint n, jobject src, jobject dst) {
     (void)cls;
-    return run(env, 0, TSX_MEM_HOST, flags, key, aad, profile, 0, descs, n, src, dst);
+    return run(env, 0, TSX_MEM_HOST, flags, key, aad, profile, 0, descs, n, src, dst, NULL);
 }
 
 /* ... at a Zstandard level: compression.zstd.level (1 - 3; 0 = the library default, 3); the library refuses any other */
 JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchLevel(
     JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jint level, jobject descs, jint n, jobject src, jobject dst) {
     (void)cls;
-    return run(env, 0, TSX_MEM_HOST, flags, key, aad, profile, level, descs, n, src, dst);
+    return run(env, 0, TSX_MEM_HOST, flags, key, aad, profile, level, descs, n, src, dst, NULL);
 }
 
 /* TSX_MEM_HOST_PACKED: dst is the upload's own buffer (a multipart part, a mapped file); chunk i lands at descs[i].dst_off */
 JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPacked(
     JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jobject descs, jint n, jobject src, jobject dst) {
     (void)cls;
-    return run(env, 0, TSX_MEM_HOST_PACKED, flags, key, aad, profile, 0, descs, n, src, dst);
+    return run(env, 0, TSX_MEM_HOST_PACKED, flags, key, aad, profile, 0, descs, n, src, dst, NULL);
 }
 
 JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedLevel(
     JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jint level, jobject descs, jint n, jobject src, jobject dst) {
     (void)cls;
-    return run(env, 0, TSX_MEM_HOST_PACKED, flags, key, aad, profile, level, descs, n, src, dst);
+    return run(env, 0, TSX_MEM_HOST_PACKED, flags, key, aad, profile, level, descs, n, src, dst, NULL);
 }
 
 JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_detransformBatch(
     JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jobject descs, jint n, jobject src, jobject dst) {
     (void)cls;
-    return run(env, 1, TSX_MEM_HOST, flags, key, aad, 1, 0, descs, n, src, dst);
+    return run(env, 1, TSX_MEM_HOST, flags, key, aad, 1, 0, descs, n, src, dst, NULL);
+}
+
+/* ---- a segment validated over several batches (tsx_records_begin / tsx_transform_batch_stream / tsx_records_result).  The state lives in
+ * a direct ByteBuffer of at least sizeof(tsx_records_state) bytes that the Java object owns; nothing here keeps a pointer to it. */
+JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_recordsBegin(JNIEnv* env, jclass cls, jobject state, jlong streamBytes) {
+    (void)cls;
+    tsx_records_state* st = state ? (tsx_records_state*)(*env)->GetDirectBufferAddress(env, state) : NULL;
+    if (!st || streamBytes < 0 || (*env)->GetDirectBufferCapacity(env, state) < (jlong)sizeof(tsx_records_state)) return TSX_E_INVAL;
+    return tsx_records_begin(st, (uint64_t)streamBytes);
+}
+
+JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchStream(
+    JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jint level, jobject descs, jint n, jobject src, jobject dst, jobject state) {
+    (void)cls;
+    return state ? run(env, 0, TSX_MEM_HOST, flags, key, aad, profile, level, descs, n, src, dst, state) : TSX_E_INVAL;
+}
+
+JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_transformBatchPackedStream(
+    JNIEnv* env, jclass cls, jint flags, jbyteArray key, jbyteArray aad, jint profile, jint level, jobject descs, jint n, jobject src, jobject dst, jobject state) {
+    (void)cls;
+    return state ? run(env, 0, TSX_MEM_HOST_PACKED, flags, key, aad, profile, level, descs, n, src, dst, state) : TSX_E_INVAL;
+}
+
+/* 1: the stream is complete, 0: not yet; info: a direct buffer of at least sizeof(tsx_records_info) bytes that receives the struct as it is */
+JNIEXPORT jint JNICALL Java_io_aiven_kafka_tieredstorage_gpu_TsxNative_recordsResult(JNIEnv* env, jclass cls, jobject state, jobject info) {
+    (void)cls;
+    const tsx_records_state* st = state ? (const tsx_records_state*)(*env)->GetDirectBufferAddress(env, state) : NULL;
+    tsx_records_info* out = info ? (tsx_records_info*)(*env)->GetDirectBufferAddress(env, info) : NULL;
+    if (!st || !out || (*env)->GetDirectBufferCapacity(env, state) < (jlong)sizeof(tsx_records_state) ||
+        (*env)->GetDirectBufferCapacity(env, info) < (jlong)sizeof(tsx_records_info)) return TSX_E_INVAL;
+    return tsx_records_result(st, out);
 }

@@ -49,6 +49,13 @@ class RecordsInfo(C.Structure):
                 ("repaired_chunks", C.c_uint32), ("ms", C.c_float), ("reserved_", C.c_uint32)]
 
 
+class RecordsState(C.Structure):
+    """tsx_records_state of include/tsxform.h: one stream of record batches between two calls of transform_batch(state=...).  The
+    caller's plain memory - it may be copied (bytes(state)) and belongs to no context."""
+    _fields_ = [("opaque", C.c_uint64 * 24)]
+assert C.sizeof(RecordsState) == 192
+
+
 class Config(C.Structure):
     """tsx_config of include/tsxform.h; fields left at CFG_DEFAULT take the library's default."""
     _fields_ = [("struct_size", C.c_uint32), ("fetch_reserved_cus", C.c_uint32), ("service_max_launch_ms", C.c_uint32), ("fetch_shared_cu_waves", C.c_uint32),
@@ -73,7 +80,8 @@ EXPORTS = ["tsx_abi_version", "tsx_version", "tsx_strerror", "tsx_init", "tsx_sh
            "tsx_ctx_create", "tsx_ctx_destroy", "tsx_ctx_timing", "tsx_transformed_bound", "tsx_transform_batch",
            "tsx_detransform_batch", "tsx_crc32c_batch", "tsx_device_malloc", "tsx_device_free", "tsx_memcpy_h2d",
            "tsx_memcpy_d2h", "tsx_ctx_device", "tsx_set_thread_device", "tsx_pool_stats", "tsx_host_register", "tsx_host_unregister",
-           "tsx_init_ex", "tsx_service_stats", "tsx_service_quiesce", "tsx_ctx_records"]
+           "tsx_init_ex", "tsx_service_stats", "tsx_service_quiesce", "tsx_ctx_records", "tsx_records_begin", "tsx_transform_batch_stream",
+           "tsx_records_result"]
 
 
 class TsxError(RuntimeError):
@@ -115,6 +123,10 @@ class Native:
             f = getattr(L, name); f.restype = C.c_int
             f.argtypes = [vp, C.POINTER(BatchParams), vp, u32, vp, sz, vp, sz, C.c_int]
         L.tsx_crc32c_batch.restype = C.c_int; L.tsx_crc32c_batch.argtypes = [vp, vp, u32, vp, sz, C.c_int]
+        L.tsx_records_begin.restype = C.c_int; L.tsx_records_begin.argtypes = [C.POINTER(RecordsState), C.c_uint64]
+        L.tsx_transform_batch_stream.restype = C.c_int
+        L.tsx_transform_batch_stream.argtypes = [vp, C.POINTER(BatchParams), vp, u32, vp, sz, vp, sz, C.c_int, C.POINTER(RecordsState)]
+        L.tsx_records_result.restype = C.c_int; L.tsx_records_result.argtypes = [C.POINTER(RecordsState), C.POINTER(RecordsInfo)]
         L.tsx_device_malloc.restype = C.c_int; L.tsx_device_malloc.argtypes = [C.c_int, sz, C.POINTER(vp)]
         L.tsx_device_free.restype = C.c_int; L.tsx_device_free.argtypes = [C.c_int, vp]
         L.tsx_memcpy_h2d.restype = C.c_int; L.tsx_memcpy_h2d.argtypes = [C.c_int, vp, vp, sz]
@@ -288,9 +300,24 @@ class Native:
             return src.nbytes
         return int((descs["src_off"] + descs["src_len"]).max()) if len(descs) else 0
 
-    def transform_batch(self, params, descs, src, dst, dst_size, mem_kind=MEM_HOST, ctx=None, src_size=None):
+    def records_begin(self, stream_bytes):
+        """A RecordsState for a stream of stream_bytes bytes in all (tsx_records_begin)."""
+        st = RecordsState()
+        self.check(self.lib.tsx_records_begin(C.byref(st), stream_bytes))
+        return st
+
+    def records_result(self, state):
+        """(complete, RecordsInfo) of the stream so far (tsx_records_result)."""
+        r = RecordsInfo()
+        return bool(self.check(self.lib.tsx_records_result(C.byref(state), C.byref(r)))), r
+
+    def transform_batch(self, params, descs, src, dst, dst_size, mem_kind=MEM_HOST, ctx=None, src_size=None, state=None):
+        """state: a RecordsState - the call's chunks continue that stream (tsx_transform_batch_stream; params.flags has VALIDATE_RECORDS)."""
         assert descs.dtype == DESC_DTYPE and descs.flags["C_CONTIGUOUS"]
         self._device_ready(mem_kind)
+        if state is not None:
+            return self.check(self.lib.tsx_transform_batch_stream(ctx, C.byref(params), descs.ctypes.data, len(descs), self._ptr(src),
+                                                                  self._src_size(descs, src, src_size), self._ptr(dst), dst_size, mem_kind, C.byref(state)))
         return self.check(self.lib.tsx_transform_batch(ctx, C.byref(params), descs.ctypes.data, len(descs), self._ptr(src),
                                                        self._src_size(descs, src, src_size), self._ptr(dst), dst_size, mem_kind))
 

@@ -11,17 +11,23 @@
 //                           exactly at its entry; otherwise the resolver walks that chunk's batches itself, from the true position, with
 //                           the same device function (repaired_chunks).  A CRC-valid batch inside a record value, a damaged first batch the
 //                           scan skipped, a hostile chunk: speculation loses and the result is still the serial walk's.
+// A call may hold a PART of a stream (tsx_transform_batch_stream; records_dev.h has the view).  The resolver then first closes the batch
+// that was open on entry - its CRC register continued over the call's bytes - chains the walkers from that batch's end instead of 0, and
+// at the call's end writes what the next call needs into the block's head: the raw bytes of a header that has not all arrived, or the open
+// batch's fields and register.  A whole stream in one call is the case in which nothing comes in and nothing goes out.
 #include <string.h>
 
 #include "records_dev.h"
 
 size_t tsx_records_block_bytes(uint32_t n) {
+    n++;                                                                // (the view's chunks)
     return sizeof(tsx_rec_head) + ((size_t)n + 1) * 8 + (size_t)n * 8 + (size_t)n * sizeof(tsx_rec_walk) + (((size_t)n * 4 + 63) & ~(size_t)63);
 }
-static_assert(sizeof(tsx_rec_head) == 64 && sizeof(tsx_rec_walk) == 40, "every part of the block begins 8-byte aligned");
+static_assert(sizeof(tsx_rec_head) == 64 + 2 * 112 && sizeof(tsx_rec_carry) == 112 && sizeof(tsx_rec_walk) == 40, "every part of the block begins 8-byte aligned");
 
 tsx_rec_block tsx_records_block_at(void* base, uint32_t n) {
     tsx_rec_block b;
+    n++;
     b.head = (tsx_rec_head*)base;
     b.pos = (uint64_t*)(b.head + 1);
     b.off = b.pos + n + 1;
@@ -30,69 +36,115 @@ tsx_rec_block tsx_records_block_at(void* base, uint32_t n) {
     return b;
 }
 
-void tsx_records_block_fill(void* h_base, const tsx_chunk_desc* descs, uint32_t n) {
+void tsx_records_block_fill(void* h_base, const tsx_chunk_desc* descs, uint32_t n, uint32_t hdr_n) {
     const tsx_rec_block b = tsx_records_block_at(h_base, n);
     memset(b.head, 0, sizeof *b.head);
-    uint64_t at = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        b.pos[i] = at; b.off[i] = descs[i].src_off; at += descs[i].src_len;
-        b.verdicts[i] = TSX_E_NOMEM;
-        memset(&b.walks[i], 0, sizeof b.walks[i]);
-    }
-    b.pos[n] = at;
+    uint64_t at = hdr_n;
+    b.pos[0] = 0; b.off[0] = 0;
+    for (uint32_t i = 0; i < n; i++) { b.pos[i + 1] = at; b.off[i + 1] = descs[i].src_off; at += descs[i].src_len; }
+    b.pos[n + 1] = at;
+    for (uint32_t i = 0; i <= n; i++) { b.verdicts[i] = TSX_E_NOMEM; memset(&b.walks[i], 0, sizeof b.walks[i]); }
 }
 
 __global__ __launch_bounds__(64) void records_walk_kernel(const tsx_crc_tables* __restrict__ tab, const uint8_t* __restrict__ src, const uint64_t* __restrict__ pos,
-                                                          const uint64_t* __restrict__ off, uint32_t n, tsx_rec_walk* __restrict__ walks) {
+                                                          const uint64_t* __restrict__ off, uint32_t n, tsx_rec_walk* __restrict__ walks,
+                                                          const uint8_t* __restrict__ carry, uint64_t total, uint64_t start) {
     __shared__ tsx_rec_lds L;
     const uint32_t k = blockIdx.x, lane = threadIdx.x;
-    tsx_rec_view v; v.src = src; v.pos = pos; v.off = off; v.n = n; v.total = pos[n];
+    tsx_rec_view v; v.src = src; v.carry = carry; v.pos = pos; v.off = off; v.n = n; v.total = total; v.avail = pos[n];
     const uint64_t lo = pos[k], hi = pos[k + 1];
     tsx_rec_walk w; w.entry = 0; w.exit = 0; w.bad_pos = 0; w.found = 0; w.batches = 0; w.compressed = 0; w.bad_reason = 0;
-    if (hi > lo) {                                                      // (uniform)
+    // `start` is the one position known to be a batch boundary (0, or the end of the batch that was open on entry): the walker of the chunk
+    // that holds it enters there, the walkers behind it guess, and a chunk in front of it lies inside the open batch - nothing begins there
+    if (hi > lo && hi > start) {                                        // (uniform)
         rec_lds_init(tab, &L, lane);
-        uint64_t entry = lo;
-        if (lo == 0 || rec_find_entry(tab, v, lo, hi, &L, lane, &entry)) rec_walk(tab, v, entry, hi, &L, lane, &w);
+        uint64_t entry = start;
+        if (lo <= start || rec_find_entry(tab, v, lo, hi, &L, lane, &entry)) rec_walk(tab, v, entry, hi, &L, lane, &w);
     }
     if (lane == 0) walks[k] = w;
 }
 
 __global__ __launch_bounds__(64) void records_resolve_kernel(const tsx_crc_tables* __restrict__ tab, const uint8_t* __restrict__ src, const uint64_t* __restrict__ pos,
                                                              const uint64_t* __restrict__ off, uint32_t n, const tsx_rec_walk* __restrict__ walks,
-                                                             int32_t* __restrict__ verdicts, tsx_rec_head* __restrict__ head) {
+                                                             int32_t* __restrict__ verdicts, tsx_rec_head* __restrict__ head, uint64_t total, uint64_t start) {
     __shared__ tsx_rec_lds L;
     const uint32_t lane = threadIdx.x;
-    tsx_rec_view v; v.src = src; v.pos = pos; v.off = off; v.n = n; v.total = pos[n];
+    tsx_rec_view v; v.src = src; v.carry = head->in.hdr; v.pos = pos; v.off = off; v.n = n; v.total = total; v.avail = pos[n];
     rec_lds_init(tab, &L, lane);
-    uint64_t at = 0, batches = 0, compressed = 0, bad_pos = ~0ull;
-    uint32_t reason = 0, repaired = 0, bad_chunk = n;
+    uint64_t at = start, batches = 0, compressed = 0, bad_pos = ~0ull;
+    uint32_t reason = 0, repaired = 0, bad_open = 0;
+    bool pending = false;
+    tsx_rec_cursor cur, ccur;                                           // the lanes' own (header bytes) and the wave's (CRC spans)
+    rec_cursor_reset(cur); rec_cursor_reset(ccur);
+    // ---- the batch that was open on entry: its register runs on over the call's bytes up to its end; a tail longer than the whole call
+    // only advances the register, and every chunk passes ----
+    const uint32_t in_open = head->in.open, in_want = head->in.want, in_comp = head->in.comp;
+    uint32_t open_reg = head->in.reg;
+    if (in_open) {                                                      // (uniform)
+        open_reg = rec_crc_reg(tab, v, ccur, 0, start < v.avail ? start : v.avail, L.tab, lane, open_reg);
+        if (start > v.avail) pending = true;
+        else if (~open_reg != in_want) { reason = TSX_REC_CRC; bad_pos = 0; bad_open = 1; }
+        else { batches++; compressed += in_comp; }
+    }
     // the walkers' results and the chunks' ends come out of pinned memory 64 chunks at a time, one load per lane: one trip over PCIe per
     // group, not one per chunk
     __shared__ tsx_rec_walk sw[64];
     __shared__ uint64_t shi[64];
-    for (uint32_t k0 = 0; k0 < n && !reason; k0 += 64) {                // (uniform)
+    for (uint32_t k0 = 0; k0 < n && !reason && !pending; k0 += 64) {    // (uniform)
         __syncthreads();
         if (k0 + lane < n) { sw[lane] = walks[k0 + lane]; shi[lane] = pos[k0 + lane + 1]; }
         __syncthreads();
-        for (uint32_t k = k0; k < n && k < k0 + 64 && !reason; k++) {
+        for (uint32_t k = k0; k < n && k < k0 + 64 && !reason && !pending; k++) {
             const uint64_t hi = shi[k - k0];
             if (at >= hi) continue;                                     // an empty chunk, or one that lies inside a batch: no batch begins here
             tsx_rec_walk w = sw[k - k0];                                // (pos[k] <= at: the chunk in front was walked up to its end)
             if (!w.found || w.entry != at) { rec_walk(tab, v, at, hi, &L, lane, &w); repaired++; }
             batches += w.batches; compressed += w.compressed;
-            if (w.bad_reason) { reason = w.bad_reason; bad_pos = w.bad_pos; bad_chunk = k; }
+            if (w.bad_reason) { reason = w.bad_reason; bad_pos = w.bad_pos; }
+            pending = (w.found & TSX_REC_WALK_PENDING) != 0;
             at = w.exit;
         }
     }
-    // the first invalid batch begins in chunk bad_chunk: that chunk and every chunk behind it are not delivered
+    // ---- what the next call needs: the batch at `at` has not all arrived (its walk has judged what it could) ----
+    tsx_rec_carry out;
+    out.open_pos = 0; out.open_end = 0; out.open = 0; out.want = 0; out.reg = 0; out.comp = 0; out.hdr_n = 0;
+    if (!reason && pending) {                                           // (uniform)
+        if (in_open && start > v.avail) { out.open = 1; out.open_end = start; out.want = in_want; out.reg = open_reg; out.comp = in_comp; }
+        else if (v.avail - at < TSX_REC_HEADER) {
+            out.hdr_n = (uint32_t)(v.avail - at);
+            if (lane < out.hdr_n) head->out.hdr[lane] = rec_byte(v, cur, at + lane);
+        } else {
+            uint8_t nb = 0;
+            if (lane < TSX_REC_HEADER) nb = rec_byte(v, cur, at + lane);
+            __syncthreads();
+            if (lane < TSX_REC_HEADER) L.hdr[lane] = nb;
+            __syncthreads();
+            out.open = 1; out.open_pos = at; out.open_end = at + 12 + (uint64_t)rec_be32(L.hdr + 8);
+            out.want = rec_be32(L.hdr + 17); out.comp = (L.hdr[22] & 7u) != 0;
+            out.reg = rec_crc_reg(tab, v, ccur, at + 21, v.avail, L.tab, lane, 0xFFFFFFFFu);
+        }
+    }
+    // the chunk that holds the first invalid batch's first byte - or the call's first byte, when the batch began in a call before - and
+    // every chunk behind it are not delivered
+    uint32_t bad_chunk = n;
+    if (reason) {                                                       // (uniform; the verdict needed a byte of this call at or behind that position)
+        const uint64_t first = pos[1];
+        rec_seek(v, cur, bad_pos > first ? bad_pos : first);
+        bad_chunk = cur.ci;
+    }
     for (uint32_t i = lane; i < n; i += 64) verdicts[i] = i >= bad_chunk ? TSX_E_RECORDS : TSX_OK;
-    if (lane == 0) { head->batches = batches; head->compressed = compressed; head->first_bad_pos = bad_pos; head->first_bad_reason = reason; head->repaired = repaired; }
+    if (lane == 0) {
+        head->batches = batches; head->compressed = compressed; head->first_bad_pos = bad_pos; head->first_bad_reason = reason; head->repaired = repaired; head->bad_open = bad_open;
+        head->out.open_pos = out.open_pos; head->out.open_end = out.open_end; head->out.open = out.open; head->out.want = out.want; head->out.reg = out.reg;
+        head->out.comp = out.comp; head->out.hdr_n = out.hdr_n;
+    }
     __threadfence_system();                                             // (every lane: the verdicts and the result before the word that says so)
     if (lane == 0) head->done = 1;
 }
 
-void tsx_launch_records(hipStream_t st, const tsx_crc_tables* d_tab, const uint8_t* src, void* hd_base, uint32_t n) {
+void tsx_launch_records(hipStream_t st, const tsx_crc_tables* d_tab, const uint8_t* src, void* hd_base, uint32_t n, uint64_t total, uint64_t start) {
     const tsx_rec_block b = tsx_records_block_at(hd_base, n);
-    hipLaunchKernelGGL(records_walk_kernel, dim3(n), dim3(64), 0, st, d_tab, src, (const uint64_t*)b.pos, (const uint64_t*)b.off, n, b.walks);
-    hipLaunchKernelGGL(records_resolve_kernel, dim3(1), dim3(64), 0, st, d_tab, src, (const uint64_t*)b.pos, (const uint64_t*)b.off, n, (const tsx_rec_walk*)b.walks, b.verdicts, b.head);
+    const uint32_t nv = n + 1;
+    hipLaunchKernelGGL(records_walk_kernel, dim3(nv), dim3(64), 0, st, d_tab, src, (const uint64_t*)b.pos, (const uint64_t*)b.off, nv, b.walks, (const uint8_t*)b.head->in.hdr, total, start);
+    hipLaunchKernelGGL(records_resolve_kernel, dim3(1), dim3(64), 0, st, d_tab, src, (const uint64_t*)b.pos, (const uint64_t*)b.off, nv, (const tsx_rec_walk*)b.walks, b.verdicts, b.head, total, start);
 }

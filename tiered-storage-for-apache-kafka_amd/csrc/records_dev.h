@@ -3,9 +3,14 @@
 // @8, partitionLeaderEpoch @12, magic @16, crc @17, attributes @21 ..., all big-endian; the CRC32C covers [21, 12 + batchLength)).
 // Internal: not part of the C ABI.
 //
-// Every length in the stream is untrusted input.  The only way to a byte of the source is rec_seek(): it takes a stream position BELOW
-// the stream's length and yields the chunk that holds it, and every caller establishes `position < total` (or `end <= total`) before it
-// asks - a damaged length yields a verdict, never an address.
+// Every length in the stream is untrusted input.  The only way to a byte of the source is rec_seek(): it takes a position BELOW the
+// call's end and yields the chunk that holds it, and every caller establishes `position < avail` (or `end <= avail`) before it asks - a
+// damaged length yields a verdict, never an address.
+//
+// A call holds a PART of a stream (tsx_transform_batch_stream; tsx_transform_batch: all of it).  Positions here are the VIEW's: position 0
+// is the first header byte carried in from the call before (chunk 0 of the view: tsx_rec_head.in.hdr, pinned memory), or the call's first
+// byte when nothing is carried.  Two lengths are kept apart: `total`, the stream's declared end, decides truncation; `avail`, the call's
+// end, decides what can be read.  avail <= total.
 #pragma once
 #include "crc_dev.h"
 
@@ -16,19 +21,20 @@
 #define TSX_REC_SCAN_MAX_LEN (1u << 20) /* ... and the longest batch it puts to the CRC, unless its own chunk is longer: a candidate is a guess, and a guess
                                            with a length of a GiB is a second of one wave's CRC (measured: 1.5 s per 1 GiB segment before this bound) */
 
-struct tsx_rec_view {                   // the stream, as the descriptors lay it out
+struct tsx_rec_view {                   // the call's part of the stream, as the descriptors lay it out
     const uint8_t* src;                 // the batch's source buffer (device addressable)
-    const uint64_t* pos;                // pos[k]: stream position of chunk k's first byte, pos[n] = the stream's length
-    const uint64_t* off;                // off[k]: chunk k's offset in src
-    uint32_t n;
-    uint64_t total;
+    const uint8_t* carry;               // chunk 0: the carried header bytes (the view's second base: off[] names offsets in src only)
+    const uint64_t* pos;                // pos[k]: position of chunk k's first byte, pos[n] = avail
+    const uint64_t* off;                // off[k]: chunk k's offset in src, k >= 1
+    uint32_t n;                         // chunks of the view: the call's + 1
+    uint64_t total, avail;
 };
 
 struct tsx_rec_cursor { uint64_t lo, hi; const uint8_t* p; uint32_t ci; };     // chunk ci holds stream positions [lo, hi) at p
 
 __device__ static inline void rec_cursor_reset(tsx_rec_cursor& c) { c.lo = 0; c.hi = 0; c.p = nullptr; c.ci = 0; }
 
-// q < v.total.  Afterwards c.lo <= q < c.hi.  The next chunk first (a walk moves forward), else the last k with pos[k] <= q by bisection:
+// q < v.avail.  Afterwards c.lo <= q < c.hi.  The next chunk first (a walk moves forward), else the last k with pos[k] <= q by bisection:
 // it is not empty, because pos[k + 1] > q.
 __device__ static inline void rec_seek(const tsx_rec_view& v, tsx_rec_cursor& c, uint64_t q) {
     if (q >= c.lo && q < c.hi) return;
@@ -41,7 +47,7 @@ __device__ static inline void rec_seek(const tsx_rec_view& v, tsx_rec_cursor& c,
         }
         k = a;
     }
-    c.ci = k; c.lo = v.pos[k]; c.hi = v.pos[k + 1]; c.p = v.src + v.off[k];
+    c.ci = k; c.lo = v.pos[k]; c.hi = v.pos[k + 1]; c.p = k ? v.src + v.off[k] : v.carry;
 }
 
 __device__ static inline uint8_t rec_byte(const tsx_rec_view& v, tsx_rec_cursor& c, uint64_t q) {
@@ -51,14 +57,15 @@ __device__ static inline uint8_t rec_byte(const tsx_rec_view& v, tsx_rec_cursor&
 
 __device__ static inline uint32_t rec_be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
 
-// CRC32C (java.util.zip.CRC32C) of stream positions [a, b), a <= b <= v.total, b - a < 2^32, by one wave; every lane calls and gets the
-// result.  cur: the wave's own (uniform) cursor - it stays where the span ended, so that a walk asks the tables (pinned memory: a read
+// The CRC32C register (java.util.zip.CRC32C without the final inversion) behind positions [a, b), a <= b <= v.avail, b - a < 2^32, for a
+// run that stood at `reg` in front of a - 0xFFFFFFFF where the checksum begins; by one wave, every lane calls and gets the result.  For A
+// followed by B the register is the register of A moved over |B| xor the run over B: a batch open across calls continues where it stood.  cur: the wave's own (uniform) cursor - it stays where the span ended, so that a walk asks the tables (pinned memory: a read
 // crosses PCIe) once per chunk it enters and not once per batch.  The span is taken apart where it crosses from one chunk to the next; of
 // each part the bytes up to the first 16-byte aligned ADDRESS go to lane 63, the whole aligned pieces to the lanes in stripes of 64-byte
 // lines (crc32c_wave's way: slicing-by-4 over the tables in ldsTab), the rest to lane 62.  Every run starts from remainder 0 and is moved
-// to the span's end with crc_pow_bytes; the init word is the remainder 0xFFFFFFFF moved over the whole span.
-__device__ static inline uint32_t rec_crc(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, tsx_rec_cursor& cur, uint64_t a, uint64_t b,
-                                          const uint32_t* ldsTab, uint32_t lane) {
+// to the span's end with crc_pow_bytes; so is `reg`, over the whole span.
+__device__ static inline uint32_t rec_crc_reg(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, tsx_rec_cursor& cur, uint64_t a, uint64_t b,
+                                              const uint32_t* ldsTab, uint32_t lane, uint32_t reg) {
     #define REC_CRC_W(x) { s ^= (x); s = ldsTab[3 * 256 + (s & 0xFF)] ^ ldsTab[2 * 256 + ((s >> 8) & 0xFF)] ^ ldsTab[256 + ((s >> 16) & 0xFF)] ^ ldsTab[s >> 24]; }
     #define REC_CRC_B(x) { s ^= (x); for (int k_ = 0; k_ < 8; k_++) s = crc_mulx(s); }
     uint32_t acc = 0;
@@ -102,7 +109,12 @@ __device__ static inline uint32_t rec_crc(const tsx_crc_tables* __restrict__ tab
     #undef REC_CRC_W
     #undef REC_CRC_B
     for (int o = 32; o; o >>= 1) acc ^= __shfl_xor(acc, o);
-    return ~(acc ^ crc_mulmod(0xFFFFFFFFu, crc_pow_bytes(tab, b - a)));
+    return acc ^ crc_mulmod(reg, crc_pow_bytes(tab, b - a));
+}
+// ... and the checksum of a span that holds all of its bytes
+__device__ static inline uint32_t rec_crc(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, tsx_rec_cursor& cur, uint64_t a, uint64_t b,
+                                          const uint32_t* ldsTab, uint32_t lane) {
+    return ~rec_crc_reg(tab, v, cur, a, b, ldsTab, lane, 0xFFFFFFFFu);
 }
 
 struct tsx_rec_lds {
@@ -118,21 +130,24 @@ __device__ static inline void rec_lds_init(const tsx_crc_tables* __restrict__ ta
     __syncthreads();
 }
 
-// The serial walk from `start` (a batch boundary, start <= stop <= total) over every batch that begins below `stop`; the whole wave
+// The serial walk from `start` (a batch boundary, start <= stop <= avail) over every batch that begins below `stop`; the whole wave
 // calls.  For each batch, in DefaultRecordBatch.ensureValid()'s order: at least a header left, batchLength >= 49 (signed), the batch
-// inside the stream, magic 2, CRC.  w->exit is where the first batch at or behind `stop` begins.  The next header's bytes are asked for
-// before the CRC of this batch runs: the load's latency passes under it.
+// inside the stream - both against `total` - magic 2, CRC.  w->exit is where the first batch at or behind `stop` begins.  A batch whose 61
+// header bytes, or whose end, lie behind the call's end cannot be judged here: the walk ends at it (TSX_REC_WALK_PENDING, w->exit) and the
+// resolver carries it into the next call.  The next header's bytes are asked for before the CRC of this batch runs: the load's latency
+// passes under it - when the call holds all 61 of them.
 __device__ static inline void rec_walk(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, uint64_t start, uint64_t stop,
                                        tsx_rec_lds* L, uint32_t lane, tsx_rec_walk* w) {
     tsx_rec_cursor cur, ccur;                                           // the lanes' own (header bytes) and the wave's (CRC spans)
     rec_cursor_reset(cur); rec_cursor_reset(ccur);
-    w->found = 1; w->entry = start; w->batches = 0; w->compressed = 0; w->bad_reason = 0; w->bad_pos = 0;
+    w->found = TSX_REC_WALK_FOUND; w->entry = start; w->batches = 0; w->compressed = 0; w->bad_reason = 0; w->bad_pos = 0;
     uint64_t pos = start;
     bool have = false;
     uint8_t nb = 0;
     while (pos < stop) {
         uint32_t why = 0;
         if (v.total - pos < TSX_REC_HEADER) why = TSX_REC_TRUNCATED;
+        else if (v.avail - pos < TSX_REC_HEADER) { w->found |= TSX_REC_WALK_PENDING; break; }
         else {
             if (!have && lane < TSX_REC_HEADER) nb = rec_byte(v, cur, pos + lane);
             __syncthreads();                                            // (the last batch's readers of hdr are done)
@@ -148,7 +163,8 @@ __device__ static inline void rec_walk(const tsx_crc_tables* __restrict__ tab, c
                 const uint32_t want = rec_be32(L->hdr + 17);
                 const uint32_t comp = (L->hdr[22] & 7u) != 0;
                 const uint64_t end = pos + 12 + (uint64_t)len;
-                if (end < stop && v.total - end >= TSX_REC_HEADER) { if (lane < TSX_REC_HEADER) nb = rec_byte(v, cur, end + lane); have = true; }
+                if (end > v.avail) { w->found |= TSX_REC_WALK_PENDING; break; }
+                if (end < stop && v.avail - end >= TSX_REC_HEADER) { if (lane < TSX_REC_HEADER) nb = rec_byte(v, cur, end + lane); have = true; }
                 if (rec_crc(tab, v, ccur, pos + 21, end, L->tab, lane) != want) why = TSX_REC_CRC;
                 else { w->batches++; w->compressed += comp; pos = end; }
             }
@@ -159,8 +175,8 @@ __device__ static inline void rec_walk(const tsx_crc_tables* __restrict__ tab, c
 }
 
 // A walker that does not know where its chunk's first batch begins: from stream positions [lo, hi) the first one that looks like a header
-// (magic 2, a length that is at least a header's, stays inside the stream and is no longer than TSX_REC_SCAN_MAX_LEN or the chunk,
-// attribute bits 7..15 zero) AND whose CRC confirms.  Returns false when there is none among the first TSX_REC_SCAN_TRIES that look like
+// (magic 2, a length that is at least a header's, ends inside the call - a candidate whose end lies behind it cannot be confirmed and is
+// skipped - and is no longer than TSX_REC_SCAN_MAX_LEN or the chunk, attribute bits 7..15 zero) AND whose CRC confirms.  Returns false when there is none among the first TSX_REC_SCAN_TRIES that look like
 // one: a chunk wholly inside a batch, a batch longer than the bound, or a hostile chunk - the resolver walks such a chunk itself.
 __device__ static inline bool rec_find_entry(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, uint64_t lo, uint64_t hi,
                                              tsx_rec_lds* L, uint32_t lane, uint64_t* entry) {
@@ -169,7 +185,7 @@ __device__ static inline bool rec_find_entry(const tsx_crc_tables* __restrict__ 
     uint32_t tries = 0;
     const uint64_t max_len = hi - lo > TSX_REC_SCAN_MAX_LEN ? hi - lo : TSX_REC_SCAN_MAX_LEN;
     for (uint64_t base = lo; base < hi; base += TSX_REC_SCAN_TILE) {
-        const uint64_t avail = v.total - base;
+        const uint64_t avail = v.avail - base;
         const uint32_t cnt = avail < TSX_REC_SCAN_TILE + 64 ? (uint32_t)avail : TSX_REC_SCAN_TILE + 64;
         const uint32_t lim = hi - base < TSX_REC_SCAN_TILE ? (uint32_t)(hi - base) : TSX_REC_SCAN_TILE;
         __syncthreads();
@@ -182,7 +198,7 @@ __device__ static inline bool rec_find_entry(const tsx_crc_tables* __restrict__ 
                 const uint8_t* h = L->tile + i;
                 if (h[16] != 2 || h[21] != 0 || (h[22] & 0x80)) continue;
                 const int32_t len = (int32_t)rec_be32(h + 8);
-                if (len < TSX_REC_MIN_LEN || (uint64_t)len > v.total - (base + i) - 12 || (uint64_t)len > max_len) continue;
+                if (len < TSX_REC_MIN_LEN || (uint64_t)len > v.avail - (base + i) - 12 || (uint64_t)len > max_len) continue;
                 best = i;
                 break;
             }

@@ -486,12 +486,12 @@ extern "C" size_t tsx_transformed_bound(size_t n, uint32_t flags) {
 }
 
 static int with_ctx(tsx_ctx* ctx, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n, const void* src, size_t src_size, void* dst,
-                    size_t dst_size, int mem_kind, int mode) {
-    if (ctx) return run_batch(ctx, params, descs, n, src, src_size, dst, dst_size, mem_kind, mode);
+                    size_t dst_size, int mem_kind, int mode, tsx_rec_stream* rs = nullptr) {
+    if (ctx) return run_batch(ctx, params, descs, n, src, src_size, dst, dst_size, mem_kind, mode, false, rs);
     int rc = TSX_OK;
     tsx_ctx* c = pool_acquire(&rc);
     if (!c) return rc;
-    rc = run_batch(c, params, descs, n, src, src_size, dst, dst_size, mem_kind, mode, true);
+    rc = run_batch(c, params, descs, n, src, src_size, dst, dst_size, mem_kind, mode, true, rs);
     pool_release(c);
     return rc;
 }
@@ -499,6 +499,39 @@ static int with_ctx(tsx_ctx* ctx, const tsx_batch_params* params, tsx_chunk_desc
 extern "C" int tsx_transform_batch(tsx_ctx* ctx, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n, const void* src,
                                    size_t src_size, void* dst, size_t dst_size, int mem_kind) {
     return with_ctx(ctx, params, descs, n, src, src_size, dst, dst_size, mem_kind, 0);
+}
+
+// ---- TSX_VALIDATE_RECORDS over several calls.  The state is the caller's memory: it is copied in, every number of it checked, worked on,
+// and copied back only when the whole call has succeeded - a negative return leaves it bit for bit as it was.
+extern "C" int tsx_records_begin(tsx_records_state* st, uint64_t stream_bytes) {
+    if (!st) return TSX_E_INVAL;
+    tsx_rec_stream s;
+    memset(&s, 0, sizeof s);
+    s.magic = TSX_REC_STATE_MAGIC; s.total = stream_bytes; s.first_bad_pos = ~0ull;
+    memcpy(st, &s, sizeof s);
+    return TSX_OK;
+}
+
+extern "C" int tsx_transform_batch_stream(tsx_ctx* ctx, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n, const void* src,
+                                          size_t src_size, void* dst, size_t dst_size, int mem_kind, tsx_records_state* st) {
+    if (!st) return TSX_E_INVAL;
+    tsx_rec_stream s;
+    memcpy(&s, st, sizeof s);
+    if (!tsx_records_state_ok(&s)) return TSX_E_INVAL;
+    const int rc = with_ctx(ctx, params, descs, n, src, src_size, dst, dst_size, mem_kind, 0, &s);
+    if (rc >= 0) memcpy(st, &s, sizeof s);
+    return rc;
+}
+
+extern "C" int tsx_records_result(const tsx_records_state* st, tsx_records_info* out) {
+    if (!st || !out) return TSX_E_INVAL;
+    tsx_rec_stream s;
+    memcpy(&s, st, sizeof s);
+    if (!tsx_records_state_ok(&s)) return TSX_E_INVAL;
+    memset(out, 0, sizeof *out);
+    out->batches = s.batches; out->compressed_batches = s.compressed; out->first_bad_pos = s.first_bad_pos; out->first_bad_reason = s.first_bad_reason;
+    out->repaired_chunks = s.repaired; out->ms = s.ms;
+    return s.consumed == s.total ? 1 : 0;
 }
 
 extern "C" int tsx_detransform_batch(tsx_ctx* ctx, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n, const void* src,

@@ -748,7 +748,7 @@ static void ctx_sync_streams(tsx_ctx* c) {
 }
 
 int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n, const void* src, size_t src_size, void* dst,
-              size_t dst_size, int mem_kind, int mode, bool pooled) {
+              size_t dst_size, int mem_kind, int mode, bool pooled, tsx_rec_stream* rs) {
     if (!descs || (n && !src) || (mode != 2 && (!params || (n && !dst)))) return TSX_E_INVAL;
     if (mem_kind != TSX_MEM_HOST && mem_kind != TSX_MEM_DEVICE && mem_kind != TSX_MEM_HOST_PACKED) return TSX_E_INVAL;
     const bool packed = mem_kind == TSX_MEM_HOST_PACKED;
@@ -771,13 +771,31 @@ int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs,
         if (mode == 0 && (flags & TSX_COMPRESS) && params->zstd_profile == TSX_ZSTD_PROFILE_DEVICE && params->zstd_level != 0) return TSX_E_UNSUPPORTED;
     }
     memset(&c->records, 0, sizeof c->records); c->records.first_bad_pos = ~0ull;
+    if (rs) {
+        // a call on a stream (the entry point has checked the state): the flag is what it is for, and it never takes more than was declared
+        if (mode != 0 || !(flags & TSX_VALIDATE_RECORDS)) return TSX_E_INVAL;
+        uint64_t bytes = 0;
+        for (uint32_t i = 0; i < n; i++) bytes += descs[i].src_len;
+        if (bytes > rs->total - rs->consumed) return TSX_E_INVAL;
+        if (rs->first_bad_reason) {
+            // the verdict has fallen in an earlier call: nothing is allocated or launched, nothing of this call is delivered
+            uint32_t max_len, max_out; size_t in_bytes; bool monotonic;
+            const int vrc = validate(descs, n, src_size, dst_size, !packed, &max_len, &max_out, &in_bytes, &monotonic);
+            if (vrc) return vrc;
+            for (uint32_t i = 0; i < n; i++) { descs[i].status = TSX_E_RECORDS; descs[i].dst_len = 0; }
+            rs->consumed += bytes;
+            tsx_records_info& o = c->records;
+            o.batches = rs->batches; o.compressed_batches = rs->compressed; o.first_bad_pos = rs->first_bad_pos; o.first_bad_reason = rs->first_bad_reason; o.repaired_chunks = rs->repaired;
+            return TSX_OK;
+        }
+    }
     if (n == 0) return TSX_OK;
     tsx_device_scope keep;
     if (hipSetDevice(c->dev->hip_id) != hipSuccess) return TSX_E_DEVICE;
     tsx_run r{};
     r.c = c; r.params = params; r.descs = descs; r.n = n; r.src = src; r.dst = dst; r.src_size = src_size; r.dst_size = dst_size; r.mode = mode;
     r.flags = flags; r.host = mem_kind != TSX_MEM_DEVICE; r.packed = packed; r.pooled = pooled;
-    r.enc = mode != 2 && (flags & TSX_ENCRYPT); r.comp = mode != 2 && (flags & TSX_COMPRESS);
+    r.enc = mode != 2 && (flags & TSX_ENCRYPT); r.comp = mode != 2 && (flags & TSX_COMPRESS); r.rs = rs;
     r.fuse_stages = r.comp && !g_cfg.stages_separate;
     const bool service = mode == 0 && r.comp;
     c->key_wiped = false; c->key_staged = false;

@@ -268,23 +268,75 @@ void gcm_verify_in_stream(const tsx_run& r, const tsx_sub& sb, hipStream_t st) {
 // stream of Kafka record batches (records.hip): TSX_E_RECORDS from the chunk on in which the first invalid batch begins.  Two ordinary
 // kernels on the context's stream, next to whatever the batch's own stages are doing (a compressing batch's waves have a second of work
 // per chunk in front of them).  Everything the kernels say comes back through the context's pinned block (tsx_internal.h: tsx_rec_block).
+// r.rs != nullptr (tsx_transform_batch_stream): the call's chunks continue the stream *r.rs describes - the host's working copy of the
+// caller's state, every number of which has been checked - and *r.rs is the state behind this call when TSX_OK is returned; the entry
+// point hands it to the caller only if the whole call succeeds.  There, a validator that cannot run fails the call (TSX_E_NOMEM): bytes
+// it has not seen must not count as consumed.
+bool tsx_records_state_ok(const tsx_rec_stream* s) {
+    if (s->magic != TSX_REC_STATE_MAGIC || s->consumed > s->total || s->hdr_n > 60 || s->hdr_n > s->consumed || s->open > 1 || s->comp > 1) return false;
+    if (s->first_bad_reason > TSX_REC_CRC || (s->first_bad_reason != 0) != (s->first_bad_pos != ~0ull) || (s->first_bad_reason && s->first_bad_pos > s->total)) return false;
+    if (s->open && (s->hdr_n || s->open_end > s->total || s->open_end <= s->consumed || s->open_pos > s->consumed || s->consumed - s->open_pos < 61 ||
+                    s->open_end - s->open_pos < 61 || s->open_end - s->open_pos > 12ull + 0x7FFFFFFFull)) return false;
+    if (s->hdr_n && s->total - (s->consumed - s->hdr_n) < 61) return false;       // (fewer than 61 bytes left is a verdict, never a carry)
+    return true;
+}
+
 int records_validate(tsx_run& r, hipEvent_t staged, int32_t* code) {
     tsx_ctx* c = r.c;
+    tsx_rec_stream* const rs = r.rs;
+    const int cannot = rs ? TSX_E_NOMEM : TSX_OK;
     for (uint32_t i = 0; i < r.n; i++) code[i] = TSX_E_NOMEM;
+    uint64_t bytes = 0;
+    for (uint32_t i = 0; i < r.n; i++) bytes += r.descs[i].src_len;
+    tsx_records_info& o = c->records;
+    if (rs && bytes == 0) {                                             // a call without bytes changes nothing
+        for (uint32_t i = 0; i < r.n; i++) code[i] = TSX_OK;
+        o.batches = rs->batches; o.compressed_batches = rs->compressed; o.first_bad_pos = rs->first_bad_pos; o.first_bad_reason = rs->first_bad_reason;
+        o.repaired_chunks = rs->repaired; o.ms = 0;
+        return TSX_OK;
+    }
     const int rc = check_block(c, tsx_records_block_bytes(r.n));
-    if (rc) return said_per_chunk(rc);
-    tsx_records_block_fill(c->h_check, r.descs, r.n);
+    if (rc) return rs ? rc : said_per_chunk(rc);
+    // the view: position 0 is the first carried header byte - stream position `origin`
+    const uint32_t hdr_n = rs ? rs->hdr_n : 0;
+    const uint64_t origin = rs ? rs->consumed - hdr_n : 0;
+    const uint64_t total = rs ? rs->total - origin : bytes;
+    const uint64_t start = rs && rs->open ? rs->open_end - origin : 0;
+    tsx_records_block_fill(c->h_check, r.descs, r.n, hdr_n);
+    const tsx_rec_block b = tsx_records_block_at(c->h_check, r.n);
+    if (rs) {
+        tsx_rec_carry& in = b.head->in;
+        in.open = rs->open; in.want = rs->want; in.reg = rs->reg; in.comp = rs->comp; in.hdr_n = hdr_n;
+        memcpy(in.hdr, rs->hdr, hdr_n);
+    }
     if (staged) HIPCHK(hipStreamWaitEvent(c->st, staged, 0));
     float ms = 0;
-    const int wrc = timed_wait(c, &ms, [&] { tsx_launch_records(c->st, c->dev->d_crc, r.d_src, c->hd_check, r.n); });
+    const int wrc = timed_wait(c, &ms, [&] { tsx_launch_records(c->st, c->dev->d_crc, r.d_src, c->hd_check, r.n, total, start); });
     if (wrc) return wrc;
     HIPCHK(hipGetLastError());
-    const tsx_rec_block b = tsx_records_block_at(c->h_check, r.n);
-    if (!__atomic_load_n(&b.head->done, __ATOMIC_ACQUIRE)) return TSX_OK;
-    for (uint32_t i = 0; i < r.n; i++) code[i] = b.verdicts[i];
-    tsx_records_info& o = c->records;
-    o.batches = b.head->batches; o.compressed_batches = b.head->compressed; o.first_bad_pos = b.head->first_bad_pos;
-    o.first_bad_reason = b.head->first_bad_reason; o.repaired_chunks = b.head->repaired;
+    if (!__atomic_load_n(&b.head->done, __ATOMIC_ACQUIRE)) return cannot;
+    for (uint32_t i = 0; i < r.n; i++) code[i] = b.verdicts[i + 1];
+    const tsx_rec_head& h = *b.head;
+    if (rs) {
+        // every number the device hands back is checked like the caller's: the state never holds what tsx_records_state_ok refuses
+        tsx_rec_stream t = *rs;
+        t.consumed += bytes; t.batches += h.batches; t.compressed += h.compressed; t.repaired += h.repaired; t.ms = ms;
+        if (h.first_bad_reason) { t.first_bad_reason = h.first_bad_reason; t.first_bad_pos = h.bad_open ? rs->open_pos : origin + h.first_bad_pos; }
+        t.hdr_n = 0; t.open = 0; t.open_pos = t.open_end = 0; t.want = t.reg = t.comp = 0; memset(t.hdr, 0, sizeof t.hdr);
+        if (!h.first_bad_reason) {
+            t.hdr_n = h.out.hdr_n;
+            if (t.hdr_n <= 60) memcpy(t.hdr, h.out.hdr, t.hdr_n);
+            const bool still = rs->open && start > bytes;               // the batch that was open on entry reaches beyond this call too
+            if (h.out.open) { t.open = 1; t.open_pos = still ? rs->open_pos : origin + h.out.open_pos;
+                              t.open_end = origin + h.out.open_end; t.want = h.out.want; t.reg = h.out.reg; t.comp = h.out.comp; }
+        }
+        if (!tsx_records_state_ok(&t)) return TSX_E_DEVICE;
+        *rs = t;
+        o.batches = t.batches; o.compressed_batches = t.compressed; o.first_bad_pos = t.first_bad_pos; o.first_bad_reason = t.first_bad_reason; o.repaired_chunks = t.repaired;
+    } else {
+        o.batches = h.batches; o.compressed_batches = h.compressed; o.first_bad_pos = h.first_bad_pos;
+        o.first_bad_reason = h.first_bad_reason; o.repaired_chunks = h.repaired;
+    }
     o.ms = ms;
     return TSX_OK;
 }

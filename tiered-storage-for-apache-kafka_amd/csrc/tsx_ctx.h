@@ -80,6 +80,7 @@ struct tsx_run {                                              // what one batch 
     int mode; uint32_t flags, max_len, max_out; bool host, packed, enc, comp, fuse_stages, pooled;
     const uint8_t* d_src; uint8_t* d_dst;
     uint8_t* zc_dst;                                          // zero-copy output: the caller's buffer as the device addresses it (then d_dst), else nullptr
+    tsx_rec_stream* rs;                                       // tsx_transform_batch_stream: the stream the call's chunks continue (records_validate), else nullptr
 };
 
 template <class T>
@@ -104,7 +105,7 @@ int reserve_or_drain(tsx_ctx* c, uint32_t n, uint32_t max_len, uint32_t max_out,
 
 // ---- tsx_batch.hip, for the entry points and the checks ----
 int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n, const void* src, size_t src_size, void* dst,
-              size_t dst_size, int mem_kind, int mode /*0 transform, 1 detransform, 2 crc only*/, bool pooled = false);
+              size_t dst_size, int mem_kind, int mode /*0 transform, 1 detransform, 2 crc only*/, bool pooled = false, tsx_rec_stream* rs = nullptr);
 // the host ranges tsx_host_register has pinned (zero-copy output asks: device_alias_of_range); forget_all: tsx_shutdown
 void registered_range_add(void* p, size_t bytes);
 void registered_range_remove(void* p);

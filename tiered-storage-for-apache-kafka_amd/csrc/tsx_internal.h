@@ -218,23 +218,57 @@ void tsx_launch_gcm_verify(hipStream_t st, const tsx_aes_tables* d_aes, const ts
 #define TSX_REC_MAGIC     3u
 #define TSX_REC_CRC       4u
 
+#define TSX_REC_WALK_FOUND   1u /* tsx_rec_walk.found: the walk had an entry */
+#define TSX_REC_WALK_PENDING 2u /* ... and ended at a batch (exit) whose header or end lies behind the call's end: the chain ends there */
 struct tsx_rec_walk {            // what one walker (or the resolver in its place) has to say about the batches that begin in its chunk
     uint64_t entry, exit;        // where its first batch begins / where the first batch at or behind the next chunk's first byte begins
     uint64_t bad_pos;            // bad_reason != 0: the first invalid batch (the walk ended there)
-    uint32_t found;              // 0: no entry (the chunk lies inside one batch, or is empty)
+    uint32_t found;              // 0: no entry (the chunk lies inside one batch, or is empty); else TSX_REC_WALK_*
     uint32_t batches, compressed, bad_reason;
 };
-struct tsx_rec_head {            // the resolver's result
+// What a stream carries over a call boundary (tsx_transform_batch_stream), in the VIEW's positions - position 0 is the first carried
+// header byte, or the call's first byte when none is carried.  At most one of the two is in use: hdr_n raw bytes of a header whose 61
+// have not all arrived, or a batch whose header has passed its checks and whose end lies behind the call's end.
+struct tsx_rec_carry {
+    uint64_t open_pos, open_end; // the open batch: where it begins (out only) and ends - in: the end is where this call's walk starts
+    uint32_t open, want, reg, comp;   // open != 0; the CRC field it expects; the raw CRC32C register over [its offset 21, the call's end); attributes & 7 != 0
+    uint32_t hdr_n, pad_[3];
+    uint8_t hdr[64];             // in: the view's chunk 0
+};
+struct tsx_rec_head {            // the resolver's result; `in` is the host's
     uint64_t batches, compressed, first_bad_pos;
-    uint32_t first_bad_reason, repaired, done, pad_[7];
+    uint32_t first_bad_reason, repaired, done, bad_open;       // bad_open: the invalid batch is the one that was open on entry (first_bad_pos: 0)
+    uint64_t pad_[3];
+    tsx_rec_carry in, out;
 };
 // One block of PINNED memory per validating batch holds everything the two kernels read and write besides the source bytes - the
-// resolver's result, the chunks' stream positions and source offsets, the walkers' results, the per-chunk verdicts: nothing small is copied
-// (a blit kernel waits behind a chip full of compressor waves), and the walkers' 40 bytes per chunk cross PCIe once each way.
+// resolver's result and the carry, the chunks' stream positions and source offsets, the walkers' results, the per-chunk verdicts: nothing
+// small is copied (a blit kernel waits behind a chip full of compressor waves), and the walkers' 40 bytes per chunk cross PCIe once each
+// way.  The view has one chunk more than the call: chunk 0 is the carried header bytes (head->in.hdr, empty in a call that carries
+// none), chunk k + 1 is the call's chunk k.
 struct tsx_rec_block { tsx_rec_head* head; uint64_t* pos; uint64_t* off; tsx_rec_walk* walks; int32_t* verdicts; };
 size_t tsx_records_block_bytes(uint32_t n);
 tsx_rec_block tsx_records_block_at(void* base, uint32_t n);
-// Host: lays the block out for descs[0 .. n) - positions, offsets, every verdict "not looked at" (TSX_E_NOMEM), head cleared.
-void tsx_records_block_fill(void* h_base, const tsx_chunk_desc* descs, uint32_t n);
-// records_walk_kernel (one wave per chunk) and records_resolve_kernel (one wave) on st; hd_base: the block as the device addresses it.
-void tsx_launch_records(hipStream_t st, const tsx_crc_tables* d_tab, const uint8_t* src, void* hd_base, uint32_t n);
+// Host: lays the block out for descs[0 .. n) behind hdr_n carried bytes - positions, offsets, every verdict "not looked at"
+// (TSX_E_NOMEM), head cleared.  n: the call's chunks (the view's n + 1 are the block's business).
+void tsx_records_block_fill(void* h_base, const tsx_chunk_desc* descs, uint32_t n, uint32_t hdr_n);
+// records_walk_kernel (one wave per chunk of the view) and records_resolve_kernel (one wave) on st; hd_base: the block as the device
+// addresses it; total: the stream's declared length and start: where the walk begins (the open batch's end, else 0), as view positions.
+void tsx_launch_records(hipStream_t st, const tsx_crc_tables* d_tab, const uint8_t* src, void* hd_base, uint32_t n, uint64_t total, uint64_t start);
+
+// A stream's state between two calls, as the host works on it (include/tsxform.h: tsx_records_state is these 192 bytes, no pointers).
+// Positions are the STREAM's.
+#define TSX_REC_STATE_MAGIC 0x5453585245435331ull
+struct tsx_rec_stream {
+    uint64_t magic, total, consumed;
+    uint64_t batches, compressed, first_bad_pos;
+    uint32_t first_bad_reason, repaired;
+    float ms; uint32_t hdr_n;    // hdr_n <= 60 carried header bytes: the stream's [consumed - hdr_n, consumed)
+    uint64_t open_pos, open_end; // open != 0: consumed < open_end <= total, open_pos + 61 <= consumed
+    uint32_t open, want, reg, comp;
+    uint8_t hdr[64];
+    uint64_t reserved_[4];
+};
+static_assert(sizeof(tsx_rec_stream) == sizeof(tsx_records_state) && sizeof(tsx_records_state) == TSX_RECORDS_STATE_BYTES, "the caller's 192 bytes");
+// every number of a caller's state, before anything is done with it
+bool tsx_records_state_ok(const tsx_rec_stream* s);

@@ -229,6 +229,7 @@ Bytes base64Decode(const std::string& s) {
 struct Backend::Fns {
     decltype(&tsx_init) init; decltype(&tsx_ctx_create) ctx_create; decltype(&tsx_ctx_destroy) ctx_destroy;
     decltype(&tsx_transform_batch) transform; decltype(&tsx_detransform_batch) detransform;
+    decltype(&tsx_records_begin) rec_begin; decltype(&tsx_transform_batch_stream) transform_stream; decltype(&tsx_records_result) rec_result;
     decltype(&tsx_crc32c_batch) crc; decltype(&tsx_transformed_bound) bound; decltype(&tsx_strerror) strerr; decltype(&tsx_version) version; decltype(&tsx_abi_version) abi;
 };
 
@@ -249,6 +250,8 @@ Backend::Backend(const std::string& libPath, int deviceIndex) : f_(new Fns), loc
     f_->ctx_destroy = (decltype(f_->ctx_destroy))sym("tsx_ctx_destroy"); f_->transform = (decltype(f_->transform))sym("tsx_transform_batch");
     f_->detransform = (decltype(f_->detransform))sym("tsx_detransform_batch"); f_->bound = (decltype(f_->bound))sym("tsx_transformed_bound");
     f_->crc = (decltype(f_->crc))sym("tsx_crc32c_batch");
+    f_->rec_begin = (decltype(f_->rec_begin))sym("tsx_records_begin"); f_->transform_stream = (decltype(f_->transform_stream))sym("tsx_transform_batch_stream");
+    f_->rec_result = (decltype(f_->rec_result))sym("tsx_records_result");
     f_->strerr = (decltype(f_->strerr))sym("tsx_strerror"); f_->version = (decltype(f_->version))sym("tsx_version");
     f_->abi = (decltype(f_->abi))sym("tsx_abi_version");
     if (f_->abi() != TSX_ABI_VERSION) throw std::runtime_error("tsxhost: ABI version mismatch");
@@ -275,6 +278,21 @@ void Backend::detransformBatch(const tsx_batch_params& p, std::vector<tsx_chunk_
     CtxLease lease(lock_->mu, ctx_);
     const int rc = f_->detransform(lease.ctx, &p, d.data(), (uint32_t)d.size(), src, srcSize, dst, dstSize, TSX_MEM_HOST);
     if (rc) throw std::runtime_error(std::string("tsx_detransform_batch: ") + f_->strerr(rc));
+}
+void Backend::recordsBegin(tsx_records_state& state, uint64_t streamBytes) {
+    const int rc = f_->rec_begin(&state, streamBytes);
+    if (rc) throw std::runtime_error(std::string("tsx_records_begin: ") + f_->strerr(rc));
+}
+void Backend::transformBatchStream(const tsx_batch_params& p, std::vector<tsx_chunk_desc>& d, const uint8_t* src, size_t srcSize, uint8_t* dst, size_t dstSize, bool packed,
+                                   tsx_records_state& state) {
+    CtxLease lease(lock_->mu, ctx_);
+    const int rc = f_->transform_stream(lease.ctx, &p, d.data(), (uint32_t)d.size(), src, srcSize, dst, dstSize, packed ? TSX_MEM_HOST_PACKED : TSX_MEM_HOST, &state);
+    if (rc) throw std::runtime_error(std::string("tsx_transform_batch_stream: ") + f_->strerr(rc));
+}
+bool Backend::recordsResult(const tsx_records_state& state, tsx_records_info& out) {
+    const int rc = f_->rec_result(&state, &out);
+    if (rc < 0) throw std::runtime_error(std::string("tsx_records_result: ") + f_->strerr(rc));
+    return rc == 1;
 }
 uint32_t Backend::crc32c(const uint8_t* data, size_t n) {
     Bytes buf(((n + 15) & ~(size_t)15) + 16);                       // the ABI wants a 16-byte aligned chunk start
@@ -457,10 +475,20 @@ Bytes BaseTransformChunkEnumeration::nextElement() {
 GpuTransformChunkEnumeration::GpuTransformChunkEnumeration(std::shared_ptr<Backend> be, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                                            std::optional<DataKeyAndAAD> enc, IvSupplier iv, int batchChunks, bool withCrc, uint32_t profile, bool readAhead,
                                                            int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify, bool recordsValidate)
+    : GpuTransformChunkEnumeration(std::move(be), std::move(inner), compress, std::move(enc), std::move(iv), batchChunks, withCrc, profile, readAhead, zstdLevel, zstdChecksum,
+                                   zstdVerify, gcmVerify, recordsValidate, -1) {}
+GpuTransformChunkEnumeration::GpuTransformChunkEnumeration(std::shared_ptr<Backend> be, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
+                                                           std::optional<DataKeyAndAAD> enc, IvSupplier iv, int batchChunks, bool withCrc, uint32_t profile, bool readAhead,
+                                                           int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify, bool recordsValidate, int64_t recordsStreamBytes)
     : be_(std::move(be)), inner_(std::move(inner)), compress_(compress), enc_(std::move(enc)), iv_(std::move(iv)), batch_(batchChunks), withCrc_(withCrc),
       profile_(profile), readAhead_(readAhead), level_(zstdLevel), checksum_(zstdChecksum), verify_(zstdVerify), gcmVerify_(gcmVerify),
-      recordsValidate_(recordsValidate) {
+      recordsValidate_(recordsValidate), recordsStreamBytes_(recordsStreamBytes) {
     if (!inner_) throw std::invalid_argument("inner cannot be null");
+    if (recordsStreamBytes_ < -1) throw std::invalid_argument("recordsStreamBytes must be -1 (off) or the segment's size, " + std::to_string(recordsStreamBytes_) + " given");
+    if (recordsValidate_ && recordsStreamBytes_ >= 0)
+        throw std::invalid_argument("segment.records.validate in one batch and streamed (recordsStreamBytes " + std::to_string(recordsStreamBytes_) + ") exclude each other");
+    memset(&recordsState_, 0, sizeof recordsState_);
+    if (recordsStreamBytes_ >= 0) be_->recordsBegin(recordsState_, (uint64_t)recordsStreamBytes_);
     if (level_ < 0 || level_ > 3) throw std::invalid_argument("zstd level must be 1, 2 or 3 (0 = library default), " + std::to_string(level_) + " given");
     if (profile_ > TSX_ZSTD_PROFILE_DEVICE) throw std::invalid_argument("unknown zstd profile " + std::to_string(profile_));
     if (profile_ == TSX_ZSTD_PROFILE_DEVICE && level_ != 0) throw std::invalid_argument("the device zstd profile has no levels, " + std::to_string(level_) + " given");
@@ -478,17 +506,43 @@ GpuTransformChunkEnumeration::~GpuTransformChunkEnumeration() {
     if (ahead_.valid()) { try { ahead_.get(); } catch (...) {} }       // the helper uses this object: it is gone before the members are
 }
 
+// One batch through the device: on the stream this object began when it validates streamed, else on its own
+void GpuTransformChunkEnumeration::runBatch(const tsx_batch_params& p, std::vector<tsx_chunk_desc>& d, const uint8_t* src, size_t srcSize, uint8_t* dst, size_t dstSize, bool packed) {
+    if (recordsStreamBytes_ < 0) {
+        if (packed) be_->transformBatchPacked(p, d, src, srcSize, dst, dstSize); else be_->transformBatch(p, d, src, srcSize, dst, dstSize);
+        return;
+    }
+    be_->transformBatchStream(p, d, src, srcSize, dst, dstSize, packed, recordsState_);
+    for (const tsx_chunk_desc& c : d) recordsConsumed_ += c.src_len;
+}
+void GpuTransformChunkEnumeration::recordsStreamDrained() {
+    if (recordsStreamBytes_ < 0) return;
+    tsx_records_info info;
+    if (!be_->recordsResult(recordsState_, info))
+        throw std::logic_error("segment.records.validate.streamed: the segment ended at " + std::to_string(recordsConsumed_) + " bytes, " + std::to_string(recordsStreamBytes_) +
+                               " were declared; it has not been validated");
+}
+std::string GpuTransformChunkEnumeration::chunkError(int status) {
+    std::string what = be_->strerror(status);
+    if (status != TSX_E_RECORDS || recordsStreamBytes_ < 0) return what;
+    tsx_records_info info;
+    be_->recordsResult(recordsState_, info);
+    static const char* const why[5] = {"none", "truncated", "length", "magic", "crc"};
+    return what + " (first invalid record batch at stream position " + std::to_string(info.first_bad_pos) + ", reason " + std::to_string(info.first_bad_reason) + " " +
+           why[info.first_bad_reason < 5 ? info.first_bad_reason : 0] + ")";
+}
+
 GpuTransformChunkEnumeration::Batch GpuTransformChunkEnumeration::transformNextBatch() {
     Batch out;
     std::vector<Bytes> in;
     while ((int)in.size() < batch_ && inner_->hasMoreElements()) in.push_back(inner_->nextElement());
-    if (in.empty()) return out;
+    if (in.empty()) { recordsStreamDrained(); return out; }
     if (recordsValidate_ && inner_->hasMoreElements())
         throw std::logic_error("segment.records.validate: the whole segment must fit one batch (batchChunks x chunk size = " + std::to_string(batch_) + " x " +
                                std::to_string(inner_->originalChunkSize()) + " bytes); it is not validated in part");
     const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u) |
-                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u);
-    if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !withCrc_ && !recordsValidate_) { out.chunks = std::move(in); return out; }     // pure base: nothing to do
+                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u) | (recordsStreamBytes_ >= 0 ? TSX_VALIDATE_RECORDS : 0u);
+    if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !withCrc_ && !(flags & TSX_VALIDATE_RECORDS)) { out.chunks = std::move(in); return out; }     // pure base: nothing to do
     std::vector<tsx_chunk_desc> d(in.size());
     size_t so = 0, dofs = 0;
     for (size_t i = 0; i < in.size(); i++) {
@@ -501,9 +555,9 @@ GpuTransformChunkEnumeration::Batch GpuTransformChunkEnumeration::transformNextB
     Bytes src(so + 16), dst(dofs + 16);
     for (size_t i = 0; i < in.size(); i++) memcpy(src.data() + d[i].src_off, in[i].data(), in[i].size());
     const tsx_batch_params p = makeParams(flags, enc_ ? &enc_->dataKey : nullptr, enc_ ? &enc_->aad : nullptr, profile_, level_);
-    be_->transformBatch(p, d, src.data(), src.size(), dst.data(), dst.size());
+    runBatch(p, d, src.data(), src.size(), dst.data(), dst.size(), false);
     for (size_t i = 0; i < in.size(); i++) {
-        if (d[i].status != TSX_OK) throw std::runtime_error(be_->strerror(d[i].status));        // the reference wraps crypto failures in RuntimeException
+        if (d[i].status != TSX_OK) throw std::runtime_error(chunkError(d[i].status));           // the reference wraps crypto failures in RuntimeException
         if (withCrc_) out.crcs.push_back(d[i].crc32c);
         out.chunks.emplace_back(dst.begin() + (long)d[i].dst_off, dst.begin() + (long)(d[i].dst_off + d[i].dst_len));
     }
@@ -524,13 +578,13 @@ GpuTransformChunkEnumeration::PackedBatch GpuTransformChunkEnumeration::transfor
     PackedBatch out;
     std::vector<Bytes> in;
     while ((int)in.size() < batch_ && inner_->hasMoreElements()) in.push_back(inner_->nextElement());
-    if (in.empty()) return out;
+    if (in.empty()) { recordsStreamDrained(); return out; }
     if (recordsValidate_ && inner_->hasMoreElements())
         throw std::logic_error("segment.records.validate: the whole segment must fit one batch (batchChunks x chunk size = " + std::to_string(batch_) + " x " +
                                std::to_string(inner_->originalChunkSize()) + " bytes); it is not validated in part");
     const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u) |
-                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u);
-    if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !recordsValidate_) {      // pure base: the chunks are the object
+                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u) | (recordsStreamBytes_ >= 0 ? TSX_VALIDATE_RECORDS : 0u);
+    if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !(flags & TSX_VALIDATE_RECORDS)) {      // pure base: the chunks are the object
         for (const Bytes& c : in) {
             out.object.insert(out.object.end(), c.begin(), c.end());
             out.sizes.push_back((int)c.size());
@@ -550,10 +604,10 @@ GpuTransformChunkEnumeration::PackedBatch GpuTransformChunkEnumeration::transfor
     for (size_t i = 0; i < in.size(); i++) if (!in[i].empty()) memcpy(src.data() + d[i].src_off, in[i].data(), in[i].size());
     const tsx_batch_params p = makeParams(flags, enc_ ? &enc_->dataKey : nullptr, enc_ ? &enc_->aad : nullptr, profile_, level_);
     out.object.resize(bound);                                          // room for the worst case, trimmed to what was produced
-    be_->transformBatchPacked(p, d, src.data(), src.size(), out.object.data(), bound);
+    runBatch(p, d, src.data(), src.size(), out.object.data(), bound, true);
     size_t total = 0;
     for (size_t i = 0; i < in.size(); i++) {
-        if (d[i].status != TSX_OK) throw std::runtime_error(be_->strerror(d[i].status));
+        if (d[i].status != TSX_OK) throw std::runtime_error(chunkError(d[i].status));
         if (withCrc_) out.crcs.push_back(d[i].crc32c);
         out.sizes.push_back((int)d[i].dst_len); total += d[i].dst_len;
     }

@@ -152,6 +152,12 @@ public:
     // the same with TSX_MEM_HOST_PACKED: transformed chunks back to back in dst, offsets and sizes returned in descs
     void transformBatchPacked(const tsx_batch_params& p, std::vector<tsx_chunk_desc>& descs, const uint8_t* src, size_t srcSize, uint8_t* dst, size_t dstSize);
     void detransformBatch(const tsx_batch_params& p, std::vector<tsx_chunk_desc>& descs, const uint8_t* src, size_t srcSize, uint8_t* dst, size_t dstSize);
+    // TSX_VALIDATE_RECORDS over several batches (tsx_records_begin / tsx_transform_batch_stream / tsx_records_result): the state is the
+    // caller's; a batch may run on the Backend's own context or on a pooled one, whichever is free
+    void recordsBegin(tsx_records_state& state, uint64_t streamBytes);
+    void transformBatchStream(const tsx_batch_params& p, std::vector<tsx_chunk_desc>& descs, const uint8_t* src, size_t srcSize, uint8_t* dst, size_t dstSize, bool packed,
+                              tsx_records_state& state);
+    bool recordsResult(const tsx_records_state& state, tsx_records_info& out);      // true: the stream is complete
     uint32_t crc32c(const uint8_t* data, size_t n);              // java.util.zip.CRC32C of one byte range (tsx_crc32c_batch)
     size_t transformedBound(size_t n, uint32_t flags) const;
     std::string strerror(int code) const;
@@ -249,6 +255,12 @@ public:
                                  int batchChunks = 64, bool withCrc = false, uint32_t zstdProfile = TSX_ZSTD_PROFILE_1_5_7, bool readAhead = true,
                                  int zstdLevel = 0, bool zstdChecksum = false, bool zstdVerify = false, bool gcmVerify = false,
                                  bool recordsValidate = false);
+    // recordsStreamBytes: -1 = off (what the constructor above passes); >= 0 = streamed validation of a segment of that many bytes
+    // (segment.records.validate.streamed): the object begins ONE stream state here and passes it with every batch - batches are issued
+    // one after another, read-ahead included - so the segment need not fit one batch.  Together with recordsValidate: std::invalid_argument.
+    GpuTransformChunkEnumeration(std::shared_ptr<Backend> backend, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
+                                 std::optional<DataKeyAndAAD> encryption, IvSupplier ivSupplier, int batchChunks, bool withCrc, uint32_t zstdProfile, bool readAhead,
+                                 int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify, bool recordsValidate, int64_t recordsStreamBytes);
     ~GpuTransformChunkEnumeration() override;
     // Zstandard level of the frames (compression.zstd.level): 0 = the library default (3, what the reference uses), 1, 2 or 3;
     // anything else is refused here, not at the first batch
@@ -270,6 +282,11 @@ public:
     // (TSX_E_RECORDS, raised like any failed chunk).  The whole segment must fit ONE batch (batchChunks x chunk size): a first batch that
     // does not exhaust `inner` is refused with std::logic_error, never validated in part.
     bool recordsValidate() const { return recordsValidate_; }
+    // the same validation over a segment streamed in several batches (segment.records.validate.streamed): the declared length of the
+    // stream, -1 = off.  A batch whose chunk fails raises what any failed chunk raises, with the first invalid batch's stream position
+    // and reason behind TSX_E_RECORDS' text; when `inner` is exhausted the stream must be complete - a segment that ended at another
+    // length than declared has not been validated and raises std::logic_error naming both numbers.
+    int64_t recordsStreamBytes() const { return recordsStreamBytes_; }
     int originalChunkSize() const override { return inner_->originalChunkSize(); }
     std::optional<int> transformedChunkSize() const override { return transformedChunkSize_; }
     bool hasMoreElements() override;
@@ -303,6 +320,12 @@ private:
     bool verify_;
     bool gcmVerify_;
     bool recordsValidate_;
+    int64_t recordsStreamBytes_;
+    tsx_records_state recordsState_;                   // the stream between two batches (recordsStreamBytes_ >= 0)
+    uint64_t recordsConsumed_ = 0;
+    void runBatch(const tsx_batch_params& p, std::vector<tsx_chunk_desc>& d, const uint8_t* src, size_t srcSize, uint8_t* dst, size_t dstSize, bool packed);
+    void recordsStreamDrained();                       // `inner` is exhausted: the stream must be complete
+    std::string chunkError(int status);                // what a failed chunk raises
     std::optional<int> transformedChunkSize_;
     std::vector<Bytes> ready_;
     size_t next_ = 0;
@@ -356,6 +379,7 @@ public:
     bool zstdVerify() const { return inner_->zstdVerify(); }
     bool gcmVerify() const { return inner_->gcmVerify(); }
     bool recordsValidate() const { return inner_->recordsValidate(); }
+    int64_t recordsStreamBytes() const { return inner_->recordsStreamBytes(); }     // (the finisher holds no options of its own: it transforms through its enumeration)
 
 private:
     bool nextBatch();

@@ -17,13 +17,18 @@ batches cross chunk boundaries wherever they fall), level 3, --callers contexts.
 and counters of the last 256-chunk batch (tsx_records_info.ms, repaired_chunks, batches) and, next to them, the separate-stage CRC
 kernels' crc_ms over the same bytes (tsx_crc32c_batch): what streaming those bytes through a CRC costs.  Default --out:
 profiles/records_level_bench.jsonl.
+--records-stream: the same segment, 5 callers, with the validation STREAMED over four calls of 64 chunks (tsx_transform_batch_stream, one state
+per segment) against the one 256-chunk call: off / streamed / one call / off in one process, and a fifth run with the same four calls per segment without
+the flag (a caller issues its calls one after another: what batches of 64 cost by themselves).  The rows carry GiB/s, the validator's time
+summed over the segment's calls (records_ms; records_ms_calls: per call of the last segment) and the pinned source a broker's upload thread
+would hold for such a batch (pinned_source_bytes: gpuBatchChunks x chunk size).  Default --out: profiles/records_stream_level_bench.jsonl.
 --device-profile: TSX_ZSTD_PROFILE_DEVICE (standard frames from the lane-parallel parse, no library's bytes) against the exact level 3 of
 profile 1.5.7 in the same process: 1.5.7 / device / device / 1.5.7 per content.  Two regimes: the `value` shape (the defaults: 5 callers,
 8 x 1 GiB) and a lone segment (--callers 1 --segments 1: one 256-chunk batch at a time).  Every row carries GiB/s, frames / original and
 the service's kernel time; the exact rows' sample is compared with libzstd's frames, the device rows' sample is opened with the oracle's
 GCM and DECODED by libzstd.  Default --out: profiles/device_profile_level_bench.jsonl.
   python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8] [--levels 3] [--checksum] [--verify]
-                              [--verify-gcm] [--records] [--device-profile] [--out FILE]"""
+                              [--verify-gcm] [--records] [--records-stream] [--device-profile] [--out FILE]"""
 import argparse
 import ctypes
 import json
@@ -85,12 +90,29 @@ def records_bench(args, emit):
     N.crc32c_batch(dc, src.data_ptr(), nat.MEM_DEVICE, ctx=ctxs[0], src_size=total)
     crc_ms = N.ctx_timing(ctxs[0]).crc_ms
     rows = []
-    for on in (False, True, True, False):
+    PER = 64                                                            # chunks per call of a streamed segment
+    last_ms = [[] for _ in range(T)]
+    # (the fifth run of --records-stream: the same four calls per segment without the flag - what the smaller batches cost by themselves)
+    for mode in (("off", "streamed", "one call", "off", "off, four calls") if args.records_stream else ("off", "one call", "one call", "off")):
+        on = not mode.startswith("off")
+        cut = mode in ("streamed", "off, four calls")
         p = nat.Native.make_params(flags | (nat.VALIDATE_RECORDS if on else 0), synth.KEY, synth.AAD, zstd_level=3)
         ds = [d.copy() for _ in range(T)]
 
         def step(t):
-            N.transform_batch(p, ds[t], src.data_ptr(), dsts[t].data_ptr(), dsts[t].numel(), nat.MEM_DEVICE, ctx=ctxs[t], src_size=total)
+            if not cut:
+                N.transform_batch(p, ds[t], src.data_ptr(), dsts[t].data_ptr(), dsts[t].numel(), nat.MEM_DEVICE, ctx=ctxs[t], src_size=total)
+                return
+            state = N.records_begin(total) if on else None
+            last_ms[t] = []
+            for lo in range(0, n, PER):
+                N.transform_batch(p, ds[t][lo:lo + PER], src.data_ptr(), dsts[t].data_ptr(), dsts[t].numel(), nat.MEM_DEVICE, ctx=ctxs[t], src_size=total, state=state)
+                if on:
+                    last_ms[t].append(N.records_result(state)[1].ms)
+            if not on:
+                return
+            done, info = N.records_result(state)
+            assert done and info.first_bad_reason == 0, (done, info.first_bad_pos, info.first_bad_reason)
         for w in range(max(args.warmup, 1)):
             for t in (range(T) if w == 0 else range(1)):
                 step(t)
@@ -109,12 +131,14 @@ def records_bench(args, emit):
         N.service_quiesce(0)
         ok = all(bool((x["status"] == 0).all()) for x in ds) and all(bool((x["dst_len"] == ds[0]["dst_len"]).all()) for x in ds)
         r = N.ctx_records(ctxs[0])
-        row = {"content": "B stream", "level": 3, "records": on, "gibs": round(args.steps * total / GiB / el, 3), "elapsed_s": round(el, 3), "chunks": n, "stream_bytes": total,
-               "steps": args.steps, "callers": T, "all_ok": bool(ok), "records_ms": round(r.ms, 3), "repaired_chunks": r.repaired_chunks, "batches": r.batches,
+        row = {"content": "B stream", "level": 3, "records": on, "mode": mode, "calls_per_segment": (n + PER - 1) // PER if cut else 1,
+               "pinned_source_bytes": (PER if cut else n) * CH, "gibs": round(args.steps * total / GiB / el, 3), "elapsed_s": round(el, 3), "chunks": n, "stream_bytes": total,
+               "steps": args.steps, "callers": T, "all_ok": bool(ok), "records_ms": round(sum(last_ms[0]) if mode == "streamed" else r.ms, 3),
+               "records_ms_calls": [round(x, 3) for x in last_ms[0]] if mode == "streamed" else None, "repaired_chunks": r.repaired_chunks, "batches": r.batches,
                "first_bad_pos": None if r.first_bad_pos == 0xFFFFFFFFFFFFFFFF else r.first_bad_pos, "crc_ms": round(crc_ms, 3), "generated_in_s": round(gen_s, 1)}
         rows.append(row)
         emit(row)
-    emit({"metric": "GiB/s of original bytes, record-batch validation off / on / on / off", "runs": [r["gibs"] for r in rows],
+    emit({"metric": "GiB/s of original bytes, record-batch validation " + " / ".join(r["mode"] for r in rows), "runs": [r["gibs"] for r in rows],
           "records_ms": [r["records_ms"] for r in rows if r["records"]], "crc_ms": crc_ms, "all_ok": all(r["all_ok"] for r in rows), "tsxform": N.version()})
 
 
@@ -132,11 +156,14 @@ def main():
     ap.add_argument("--verify", action="store_true", help="each level without and with TSX_VERIFY, alternating")
     ap.add_argument("--verify-gcm", action="store_true", help="each level without and with TSX_VERIFY_GCM, alternating")
     ap.add_argument("--records", action="store_true", help="TSX_VALIDATE_RECORDS off / on / on / off on one valid segment of content B")
+    ap.add_argument("--records-stream", action="store_true", help="the same segment: off / streamed in four calls of 64 chunks / one 256-chunk call / off")
     ap.add_argument("--device-profile", action="store_true", help="profile 1.5.7 level 3 / device / device / 1.5.7 in one process")
     ap.add_argument("--out", default=None, help="append every JSON line to this file as well")
     args = ap.parse_args()
     if args.device_profile and not args.out:
         args.out = os.path.join(ROOT, "profiles", "device_profile_level_bench.jsonl")
+    if args.records_stream and not args.out:
+        args.out = os.path.join(ROOT, "profiles", "records_stream_level_bench.jsonl")
     if args.records and not args.out:
         args.out = os.path.join(ROOT, "profiles", "records_level_bench.jsonl")
     if args.verify_gcm and not args.out:
@@ -149,7 +176,7 @@ def main():
             with open(args.out, "a") as f:
                 f.write(line + "\n")
 
-    if args.records:
+    if args.records or args.records_stream:
         return records_bench(args, emit)
     import torch  # before libtsxform: one shared HIP runtime
     import tsxform
