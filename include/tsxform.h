@@ -89,9 +89,35 @@ extern "C" {
  * the flag set no chunk is reported TSX_OK whose bytes the validator has not covered (TSX_E_NOMEM when it finds no memory).  The
  * validator's kernels are ordinary kernels that run while the batch's own stages do (next to the compressor service the batch counts as
  * a fetch having been seen); tsx_ctx_records() describes what they found.  With the flag clear nothing is allocated or launched.
- * NOT covered: the framing of the records inside a batch, the order of offsets, compressed payloads; message sets of magic 0 / 1 fail
- * (reason 3).  Detransform accepts and ignores the flag.  (0x10 and 0x40 stay unassigned.) */
+ * Covered only with TSX_VALIDATE_FRAMES (below): the framing of the records inside a batch and the order of offsets.  NOT covered with
+ * either flag: compressed payloads; message sets of magic 0 / 1 fail (reason 3).  Detransform accepts and ignores the flag.  (0x10 and
+ * 0x40 stay unassigned.) */
 #define TSX_VALIDATE_RECORDS 0x100u
+/* Modifier of TSX_VALIDATE_RECORDS on tsx_transform_batch (without it: TSX_E_INVAL): every batch that has passed its CRC is examined
+ * further, in stream order, and counts as valid only if it passes.  The first failing check of the first failing batch decides, with
+ * the same statuses as above.  Header fields big-endian: baseOffset i64 @0, lastOffsetDelta i32 @23, recordsCount i32 @57; the records
+ * occupy [position + 61, the batch's end).
+ *   1. offsets (reason 6): baseOffset >= 0; lastOffsetDelta >= 0; baseOffset + lastOffsetDelta does not overflow an i64; baseOffset is
+ *      greater than the baseOffset + lastOffsetDelta of the valid batch in front (the stream's first batch has none).  Every batch,
+ *      compressed ones included.  This is what catches damage to baseOffset, which lies outside the CRC - as far as it breaks the order:
+ *      a flipped low bit that leaves the batch between its neighbours passes.
+ *   2. count (reason 5): recordsCount >= 0.
+ *   3. records, of an uncompressed batch (attributes & 7 == 0; control batches included): exactly recordsCount records are read from
+ *      position + 61 the way DefaultRecord.readFrom reads them - varints and varlongs as ByteUtils.readVarint / readVarlong (zigzag; at
+ *      most 5 / 10 bytes, a continuation bit on the last is malformed; excess bits of a 5th byte are dropped).  Per record, in wire order:
+ *      length >= 0 and the body inside the batch; attributes; timestampDelta; offsetDelta with 0 <= delta <= lastOffsetDelta and greater
+ *      than the record's in front (a violation is reason 6); keyLength >= -1 and the key; valueLength >= -1 and the value; headersCount
+ *      >= 0, per header a key length >= 0 with its bytes and a value length >= -1 with its bytes; the fields end exactly at the body's end.
+ *      A field that would leave its record, or a record its batch, is a verdict, never an address.  Everything but the offsetDelta rule
+ *      is reason 5.  The lowest-numbered failing record decides, within it the first failing field.  Behind the last record the position
+ *      must be the batch's end (reason 5).  An empty batch (recordsCount 0, nothing behind the header), as compaction leaves them, passes
+ *      whatever its lastOffsetDelta.
+ * NOT checked: timestamps, the order of partitionLeaderEpoch, producer id / epoch / sequence, the payloads of compressed batches - and
+ * the streamed form: tsx_transform_batch_stream refuses the flag with TSX_E_UNSUPPORTED (the records of a batch that is open across two
+ * calls cannot be walked without buffering the batch).  A record is read by one lane: a hostile batch that is ONE record of a GiB of
+ * empty headers, sealed with a valid CRC, costs that lane a walk over all of it.  Detransform accepts and ignores the flag.  With the
+ * flag clear nothing changes - the same kernels, launches and allocations.  (0x10, 0x40 and 0x200 stay unassigned.) */
+#define TSX_VALIDATE_FRAMES 0x400u
 
 /* where src/dst live */
 /* host pointers.  The batch is cut into pieces whose H2D copy, kernels and D2H copy overlap: pieces of >= 64 MiB in order on three
@@ -152,7 +178,7 @@ typedef struct tsx_chunk_desc {
 /* Per-batch parameters: one (data key, AAD) pair per segment
  * (AesEncryptionProvider.createDataKeyAndAAD, core/.../security/AesEncryptionProvider.java:52-58). */
 typedef struct tsx_batch_params {
-    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC [| TSX_ZSTD_CHECKSUM] [| TSX_VERIFY] [| TSX_VERIFY_GCM] [| TSX_VALIDATE_RECORDS] */
+    uint32_t flags;        /* TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC [| TSX_ZSTD_CHECKSUM] [| TSX_VERIFY] [| TSX_VERIFY_GCM] [| TSX_VALIDATE_RECORDS [| TSX_VALIDATE_FRAMES]] */
     uint32_t aad_len;      /* reference: 32                                                         */
     uint8_t  key[32];      /* AES-256 data key (SecretKey.getEncoded())                             */
     uint8_t  aad[64];
@@ -251,12 +277,14 @@ typedef struct tsx_records_info {
     uint64_t compressed_batches;  /* ... of which attributes & 7 != 0 (what compression.heuristic.enabled asks, for the whole segment) */
     uint64_t first_bad_pos;       /* stream offset of the first invalid batch, or UINT64_MAX                                         */
     uint32_t first_bad_reason;    /* 0 none; 1 truncated (fewer than 61 bytes left, or the batch reaches beyond the stream's end);
-                                     2 length (batchLength < 49); 3 magic; 4 crc                                                     */
+                                     2 length (batchLength < 49); 3 magic; 4 crc; with TSX_VALIDATE_FRAMES also 5 records (the
+                                     count or the framing of the batch's records) and 6 offsets (of the batch or of a record)        */
     uint32_t repaired_chunks;     /* chunks whose batches the resolver walked itself: the chunk's own walker had found no entry, or
                                      another one than the chain arrives at (a CRC-valid batch inside a record value, a damaged first
                                      batch)                                                                                          */
     float    ms;                  /* the validator's kernels, by events                                                              */
-    uint32_t reserved_;
+    uint32_t records;             /* TSX_VALIDATE_FRAMES: sum of recordsCount over the valid uncompressed batches in front of the first
+                                     invalid batch - the records actually read (saturates at UINT32_MAX); 0 without the flag         */
 } tsx_records_info;
 int  tsx_ctx_records(const tsx_ctx* ctx, tsx_records_info* out);
 int  tsx_ctx_device(const tsx_ctx* ctx);                /* device index (0 .. tsx_device_count()-1) the ctx lives on */
@@ -326,6 +354,8 @@ int tsx_records_begin(tsx_records_state* st, uint64_t stream_bytes);
 /* tsx_transform_batch in every respect - every mem_kind, ctx == NULL from the pool, every chain - except that the call's chunks CONTINUE
  * the stream st describes instead of being a stream of their own.
  *   - params->flags must contain TSX_VALIDATE_RECORDS, else TSX_E_INVAL.
+ *   - params->flags with TSX_VALIDATE_FRAMES: TSX_E_UNSUPPORTED before anything is touched - a batch that is open across two calls
+ *     cannot have its records walked without buffering it, which is not built.  The state stays bit for bit.
  *   - bytes consumed so far + the call's src_len sum > the declared length: TSX_E_INVAL before anything is touched.
  *   - every number in the state is checked on entry (carried header bytes <= 60, consumed <= declared, the open batch's end <= declared,
  *     ...): a state that was never begun, or a damaged one, is TSX_E_INVAL.  A length yields a verdict, never an address.

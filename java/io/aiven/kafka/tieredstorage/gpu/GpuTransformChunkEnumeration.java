@@ -41,6 +41,7 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
     private final boolean gcmVerify;         // every delivered IV || C || TAG is decrypted and authenticated on the device
     private final boolean recordsValidate;   // the source, as one stream, is walked on the device as a Kafka v2 log
     private final long recordsStreamBytes;   // >= 0: the same walk over a segment of that many bytes, streamed in several batches; -1: off
+    private final boolean recordsFrames;     // ... and behind each batch's CRC its offsets, its count and the framing of its records
     private final ByteBuffer recordsState;   // ... the one stream state, passed with every batch (a tsx_records_state)
     private long recordsConsumed;            // ... source bytes the batches so far have held
     private final int device;
@@ -184,6 +185,30 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
                                         final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
                                         final boolean zstdVerify, final boolean gcmVerify, final boolean recordsValidate,
                                         final long recordsStreamBytes) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, readAhead, zstdLevel,
+            zstdChecksum, zstdVerify, gcmVerify, recordsValidate, recordsStreamBytes, false);
+    }
+
+    /**
+     * @param recordsFrames with {@code recordsValidate}, plugin configuration key {@code segment.records.validate.frames} (INTEGRATION.md 2),
+     *                  default false: every record batch that has passed its CRC is examined further on the device
+     *                  ({@link TsxNative#VALIDATE_FRAMES}) - the order of base offsets from batch to batch, which catches damage to
+     *                  {@code baseOffset} (it lies outside the CRC); the record count; and for an uncompressed batch the varint framing
+     *                  and the offset deltas of every record, as DefaultRecord.readFrom would find them on a consumer's fetch.  Without
+     *                  {@code recordsValidate}, or together with the streamed form ({@code recordsStreamBytes >= 0}: a batch open across
+     *                  two device calls cannot have its records walked), it is refused.
+     */
+    public GpuTransformChunkEnumeration(final TransformChunkEnumeration inner, final boolean compress,
+                                        final DataKeyAndAAD keyAndAad, final int batchChunks,
+                                        final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                        final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
+                                        final boolean zstdVerify, final boolean gcmVerify, final boolean recordsValidate,
+                                        final long recordsStreamBytes,
+                                        final boolean recordsFrames) {
+        if (recordsFrames && (!recordsValidate || recordsStreamBytes >= 0)) {
+            throw new IllegalArgumentException("segment.records.validate.frames needs segment.records.validate, and not the streamed form");
+        }
+        this.recordsFrames = recordsFrames;
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
         this.recordsValidate = recordsValidate;
         if (recordsStreamBytes < -1) {
@@ -352,7 +377,8 @@ public class GpuTransformChunkEnumeration implements TransformChunkEnumeration {
             | (zstdVerify ? TsxNative.VERIFY : 0)
             | (gcmVerify ? TsxNative.VERIFY_GCM : 0)
             | (recordsValidate ? TsxNative.VALIDATE_RECORDS : 0)
-            | (recordsStreamBytes >= 0 ? TsxNative.VALIDATE_RECORDS : 0);
+            | (recordsStreamBytes >= 0 ? TsxNative.VALIDATE_RECORDS : 0)
+            | (recordsFrames ? TsxNative.VALIDATE_FRAMES : 0);
         // per-thread, reused, pinned (registered with the device): the compressor waves write every chunk's IV || C || TAG straight into the
         // dst buffer's slots (zero-copy output, DESIGN.md section 1) - a pageable buffer would send the batch through copy engines instead.
         // Footprint per thread: ~2.1 GiB at 256 x 4 MiB (source batch + bound-sized output slots), INTEGRATION.md section 4.

@@ -126,6 +126,7 @@ public class GpuTransformFinisher {
     private final boolean gcmVerify;         // every delivered IV || C || TAG is decrypted and authenticated on the device
     private final boolean recordsValidate;   // the source, as one stream, is walked on the device as a Kafka v2 log
     private final long recordsStreamBytes;   // >= 0: the same walk over a segment of that many bytes, streamed in several batches; -1: off
+    private final boolean recordsFrames;     // ... and behind each batch's CRC its offsets, its count and the framing of its records
     private final ByteBuffer recordsState;   // ... the one stream state, passed with every batch (a tsx_records_state)
     private long recordsConsumed;            // ... source bytes the batches so far have held
     private final int device;
@@ -250,6 +251,30 @@ public class GpuTransformFinisher {
                                 final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
                                 final boolean zstdVerify, final boolean gcmVerify, final boolean recordsValidate,
                                 final long recordsStreamBytes) {
+        this(inner, compress, keyAndAad, batchChunks, random, zstdProfile, segmentHash, originalFileSize, chunkingEnabled, rateLimitingBucket, readAhead, zstdLevel,
+            zstdChecksum, zstdVerify, gcmVerify, recordsValidate, recordsStreamBytes, false);
+    }
+
+    /**
+     * @param recordsFrames with {@code recordsValidate}, plugin configuration key {@code segment.records.validate.frames} (INTEGRATION.md 2),
+     *                  default false: every record batch that has passed its CRC is examined further on the device
+     *                  ({@link TsxNative#VALIDATE_FRAMES}) - the order of base offsets from batch to batch, which catches damage to
+     *                  {@code baseOffset} (it lies outside the CRC); the record count; and for an uncompressed batch the varint framing
+     *                  and the offset deltas of every record, as DefaultRecord.readFrom would find them on a consumer's fetch.  Without
+     *                  {@code recordsValidate}, or together with the streamed form ({@code recordsStreamBytes >= 0}: a batch open across
+     *                  two device calls cannot have its records walked), it is refused.
+     */
+    public GpuTransformFinisher(final TransformChunkEnumeration inner, final boolean compress, final DataKeyAndAAD keyAndAad,
+                                final int batchChunks, final SecureRandom random, final int zstdProfile, final int segmentHash,
+                                final int originalFileSize, final boolean chunkingEnabled, final Bucket rateLimitingBucket,
+                                final boolean readAhead, final int zstdLevel, final boolean zstdChecksum,
+                                final boolean zstdVerify, final boolean gcmVerify, final boolean recordsValidate,
+                                final long recordsStreamBytes,
+                                final boolean recordsFrames) {
+        if (recordsFrames && (!recordsValidate || recordsStreamBytes >= 0)) {
+            throw new IllegalArgumentException("segment.records.validate.frames needs segment.records.validate, and not the streamed form");
+        }
+        this.recordsFrames = recordsFrames;
         this.inner = Objects.requireNonNull(inner, "inner cannot be null");
         this.recordsValidate = recordsValidate;
         if (recordsStreamBytes < -1) {
@@ -330,7 +355,8 @@ public class GpuTransformFinisher {
             | (zstdVerify ? TsxNative.VERIFY : 0)
             | (gcmVerify ? TsxNative.VERIFY_GCM : 0)
             | (recordsValidate ? TsxNative.VALIDATE_RECORDS : 0)
-            | (recordsStreamBytes >= 0 ? TsxNative.VALIDATE_RECORDS : 0);
+            | (recordsStreamBytes >= 0 ? TsxNative.VALIDATE_RECORDS : 0)
+            | (recordsFrames ? TsxNative.VALIDATE_FRAMES : 0);
     }
 
     /** What a failed chunk raises: the code's text and, for a streamed validation's {@link TsxNative#E_RECORDS}, where and why. */

@@ -36,6 +36,13 @@ public final class TsxNative {
      * status {@link #E_RECORDS}.  Detransform accepts and ignores the flag.
      */
     public static final int VALIDATE_RECORDS = 0x100;
+    /**
+     * With {@link #VALIDATE_RECORDS} on {@code transformBatch} ({@code segment.records.validate.frames}): every batch that has passed its
+     * CRC is examined further - the order of base offsets from batch to batch, the record count, and for an uncompressed batch the varint
+     * framing and the offset deltas of every record.  Without {@link #VALIDATE_RECORDS} the call is refused; the streamed form
+     * ({@code transformBatchStream}) refuses the flag.  Detransform accepts and ignores it.
+     */
+    public static final int VALIDATE_FRAMES = 0x400;
 
     public static final int OK = 0;
     public static final int E_TAG_MISMATCH = -5;

@@ -17,6 +17,7 @@ ZSTD_CHECKSUM = 8        # with COMPRESS on transform: frames carry a content ch
 VERIFY = 0x20            # with COMPRESS on transform: every frame is read back and compared with its chunk before it is reported (TSX_VERIFY)
 VERIFY_GCM = 0x80        # with ENCRYPT on transform: the delivered IV||C||TAG of every chunk is decrypted and authenticated on the device before it is reported (TSX_VERIFY_GCM)
 VALIDATE_RECORDS = 0x100 # on transform: the batch's source, as ONE stream, is walked on the device as a Kafka v2 log before it is reported (TSX_VALIDATE_RECORDS)
+VALIDATE_FRAMES = 0x400  # with VALIDATE_RECORDS on transform_batch: every CRC-valid batch's offsets, record count and record framing are checked too (TSX_VALIDATE_FRAMES)
 MEM_HOST, MEM_DEVICE, MEM_HOST_PACKED = 0, 1, 2
 OK, E_INVAL, E_DEVICE, E_NOMEM, E_DST_TOO_SMALL, E_TAG_MISMATCH, E_BAD_FRAME, E_BAD_SIZE, E_SHORT_CHUNK, E_UNSUPPORTED = \
     0, -1, -2, -3, -4, -5, -6, -7, -8, -9
@@ -47,6 +48,15 @@ class RecordsInfo(C.Structure):
     """tsx_records_info of include/tsxform.h: what VALIDATE_RECORDS found in the last batch on a context."""
     _fields_ = [("batches", C.c_uint64), ("compressed_batches", C.c_uint64), ("first_bad_pos", C.c_uint64), ("first_bad_reason", C.c_uint32),
                 ("repaired_chunks", C.c_uint32), ("ms", C.c_float), ("reserved_", C.c_uint32)]
+
+    @property
+    def records(self):
+        """The struct's last word under its name in the header: with VALIDATE_FRAMES the records read, else 0."""
+        return self.reserved_
+
+    @records.setter
+    def records(self, v):
+        self.reserved_ = v
 
 
 class RecordsState(C.Structure):

@@ -117,17 +117,149 @@ __device__ static inline uint32_t rec_crc(const tsx_crc_tables* __restrict__ tab
     return ~rec_crc_reg(tab, v, cur, a, b, ldsTab, lane, 0xFFFFFFFFu);
 }
 
-struct tsx_rec_lds {
+// FRAMES (TSX_VALIDATE_FRAMES): the tile also stages the records of the batch under examination, and is 640 bytes longer - with them the
+// LDS of both frames kernels is a whole number of 1280-byte allocation granules (walker 7, resolver 11).
+#define TSX_REC_FRAMES_MORE 640u
+template <bool FRAMES> struct tsx_rec_lds_t {
     uint32_t tab[4 * 256];                                              // slicing tables 0..3 of tsx_crc_tables
     uint8_t hdr[64];                                                    // the header of the batch under examination
-    uint8_t tile[TSX_REC_SCAN_TILE + 64];                               // a walker without an entry: the bytes it looks for one in
+    uint8_t tile[TSX_REC_SCAN_TILE + 64 + (FRAMES ? TSX_REC_FRAMES_MORE : 0u)];   // a walker without an entry: the bytes it looks for one in
 };
+typedef tsx_rec_lds_t<false> tsx_rec_lds;
 
-__device__ static inline void rec_lds_init(const tsx_crc_tables* __restrict__ tab, tsx_rec_lds* L, uint32_t lane) {
+template <class LDS>
+__device__ static inline void rec_lds_init(const tsx_crc_tables* __restrict__ tab, LDS* L, uint32_t lane) {
     const uint4* g = reinterpret_cast<const uint4*>(&tab->slice[0][0]);
     uint4* l = reinterpret_cast<uint4*>(L->tab);
     for (uint32_t i = lane; i < 4 * 256 / 4; i += 64) l[i] = g[i];
     __syncthreads();
+}
+
+// ---- TSX_VALIDATE_FRAMES: the records of one batch --------------------------------------------------------------------------------------
+// A reader of the record region: a staged tile in LDS (stream positions [tb, tb + cnt)), and rec_byte() for whatever lies outside it - a
+// varint behind a key or value longer than the tile.  Every caller establishes `q < lim <= end <= avail` before it asks.
+struct tsx_rec_reader { tsx_rec_cursor cur; const uint8_t* tile; uint64_t tb; uint32_t cnt; };
+
+__device__ static inline uint32_t rec_rd(const tsx_rec_view& v, tsx_rec_reader& r, uint64_t q) {
+    const uint64_t d = q - r.tb;                                        // (q < tb wraps: not in the tile)
+    return d < r.cnt ? r.tile[d] : rec_byte(v, r.cur, q);
+}
+
+// ByteUtils.readVarint: zigzag, at most 5 bytes, a continuation bit on the 5th is malformed, the 5th byte's excess bits fall off the int.
+// false: malformed, or it would leave [q, lim).  q moves behind it.
+__device__ static inline bool rec_varint(const tsx_rec_view& v, tsx_rec_reader& r, uint64_t& q, uint64_t lim, int32_t* out) {
+    uint32_t val = 0;
+    for (uint32_t i = 0; i < 5; i++) {
+        if (q >= lim) return false;
+        const uint32_t b = rec_rd(v, r, q++);
+        val |= (b & 0x7Fu) << (7 * i);
+        if (!(b & 0x80u)) { *out = (int32_t)(val >> 1) ^ -(int32_t)(val & 1u); return true; }
+    }
+    return false;
+}
+// ByteUtils.readVarlong: at most 10 bytes; its value (a timestamp delta) is not looked at
+__device__ static inline bool rec_varlong_skip(const tsx_rec_view& v, tsx_rec_reader& r, uint64_t& q, uint64_t lim) {
+    for (uint32_t i = 0; i < 10; i++) {
+        if (q >= lim) return false;
+        if (!(rec_rd(v, r, q++) & 0x80u)) return true;
+    }
+    return false;
+}
+// a length varint >= min_len and, when positive, that many bytes inside [q, lim)
+__device__ static inline bool rec_sized(const tsx_rec_view& v, tsx_rec_reader& r, uint64_t& q, uint64_t lim, int32_t min_len) {
+    int32_t n;
+    if (!rec_varint(v, r, q, lim, &n) || n < min_len) return false;
+    if (n > 0) { if ((uint64_t)n > lim - q) return false; q += (uint64_t)n; }
+    return true;
+}
+
+// One record's fields behind its length, body [b, e), e <= end: DefaultRecord.readFrom's order.  Returns the reason of the first field
+// that fails (0: none).  *delta, *have: the record's offsetDelta, once it has been read (its order against the record in front is the
+// caller's to check, and outranks what this returns when it fails: the offsetDelta stands in front of the key).
+__device__ static inline uint32_t rec_record_fields(const tsx_rec_view& v, tsx_rec_reader& r, uint64_t b, uint64_t e, int32_t last_delta, int32_t* delta, bool* have) {
+    uint64_t q = b;
+    if (q >= e) return TSX_REC_RECORDS;                                 // attributes
+    q++;
+    if (!rec_varlong_skip(v, r, q, e)) return TSX_REC_RECORDS;          // timestampDelta
+    int32_t d;
+    if (!rec_varint(v, r, q, e, &d)) return TSX_REC_RECORDS;            // offsetDelta
+    *delta = d; *have = true;
+    if (d < 0 || d > last_delta) return TSX_REC_OFFSETS;
+    if (!rec_sized(v, r, q, e, -1)) return TSX_REC_RECORDS;             // key
+    if (!rec_sized(v, r, q, e, -1)) return TSX_REC_RECORDS;             // value
+    int32_t nh;
+    if (!rec_varint(v, r, q, e, &nh) || nh < 0) return TSX_REC_RECORDS; // headers: every one takes two bytes or more, the body bounds the loop
+    for (int32_t h = 0; h < nh; h++)
+        if (!rec_sized(v, r, q, e, 0) || !rec_sized(v, r, q, e, -1)) return TSX_REC_RECORDS;
+    return q == e ? 0u : TSX_REC_RECORDS;
+}
+
+// The records of one uncompressed batch whose CRC has passed: exactly `count` (>= 0) records in [from, end), end <= avail; the whole wave
+// calls and gets the reason (0, TSX_REC_RECORDS, TSX_REC_OFFSETS) of the lowest-numbered record that fails.  Trip by trip: the region from
+// the next record on is staged into the tile (coalesced), every lane follows the chain of length varints through it - the same LDS words
+// for all, one dependent hop per record, up to 64 records that BEGIN in the tile - and keeps the bounds of record `lane`; then each lane
+// reads its record's fields.  A record that reaches beyond the tile is read through rec_byte() where it must be (its varints), and its key
+// and value are stepped over by arithmetic.
+template <class LDS>
+__device__ static inline uint32_t rec_frames_records(const tsx_rec_view& v, uint64_t from, uint64_t end, int32_t count, int32_t last_delta, LDS* L, uint32_t lane) {
+    tsx_rec_reader r;
+    rec_cursor_reset(r.cur); r.tile = L->tile; r.tb = 0; r.cnt = 0;
+    uint64_t q = from;
+    int32_t prev = -1;
+    for (uint32_t done = 0; done < (uint32_t)count;) {                  // (uniform)
+        const uint64_t left = end - q;
+        const uint32_t cnt = left < sizeof L->tile ? (uint32_t)left : (uint32_t)sizeof L->tile;
+        __syncthreads();                                                // (the last trip's readers of the tile are done)
+        for (uint32_t i = lane; i < cnt; i += 64) L->tile[i] = rec_byte(v, r.cur, q + i);
+        __syncthreads();
+        r.tb = q; r.cnt = cnt;
+        const uint32_t want = (uint32_t)count - done < 64u ? (uint32_t)count - done : 64u;
+        uint32_t m = 0;
+        bool chain_bad = false;
+        uint64_t s = q, my_b = 0, my_e = 0;
+        while (m < want) {
+            if (s >= end) { chain_bad = true; break; }                  // more records counted than the batch holds
+            if (s - q >= cnt) break;                                    // the next record begins behind the tile (m >= 1: s == q is inside it)
+            uint64_t t = s;
+            int32_t len;
+            if (!rec_varint(v, r, t, end, &len) || len < 0 || (uint64_t)len > end - t) { chain_bad = true; break; }
+            if (m == lane) { my_b = t; my_e = t + (uint64_t)len; }
+            s = t + (uint64_t)len; m++;
+        }
+        uint32_t why = 0;
+        int32_t d = 0;
+        bool have = false;
+        if (lane < m) why = rec_record_fields(v, r, my_b, my_e, last_delta, &d, &have);
+        int32_t pd = __shfl_up(d, 1);
+        uint32_t ph = __shfl_up((uint32_t)have, 1);
+        if (lane == 0) { pd = prev; ph = 1; }
+        if (lane < m && have && ph && d <= pd) why = TSX_REC_OFFSETS;   // (a record in front without a delta has failed, and decides)
+        uint32_t key = why ? lane << 3 | why : 0xFFFFFFFFu;
+        if (chain_bad && lane == m) key = m << 3 | TSX_REC_RECORDS;     // (m < 64)
+        for (int o = 32; o; o >>= 1) { const uint32_t x = __shfl_xor(key, o); key = x < key ? x : key; }
+        if (key != 0xFFFFFFFFu) return key & 7u;
+        prev = __shfl(d, (int)m - 1);
+        done += m; q = s;
+    }
+    return q == end ? 0u : TSX_REC_RECORDS;                             // a count too small leaves bytes over
+}
+
+__device__ static inline int64_t rec_be64s(const uint8_t* p) { return (int64_t)((uint64_t)rec_be32(p) << 32 | rec_be32(p + 4)); }
+
+// The checks of TSX_VALIDATE_FRAMES on a batch at `pos` whose CRC has passed and whose header is in L->hdr; the whole wave calls.  have_prev,
+// prev_last: baseOffset + lastOffsetDelta of the valid batch in front, when the caller knows it.  Returns the reason (0: valid) and the
+// header's baseOffset, last offset and recordsCount.
+template <class LDS>
+__device__ static inline uint32_t rec_frames_batch(const tsx_rec_view& v, uint64_t pos, uint64_t end, bool comp, bool have_prev, int64_t prev_last,
+                                                   LDS* L, uint32_t lane, int64_t* base_out, int64_t* last_out, int32_t* count_out) {
+    const int64_t base = rec_be64s(L->hdr);
+    const int32_t last_delta = (int32_t)rec_be32(L->hdr + 23), count = (int32_t)rec_be32(L->hdr + 57);
+    *base_out = base; *count_out = count; *last_out = 0;
+    if (base < 0 || last_delta < 0 || base > INT64_MAX - (int64_t)last_delta || (have_prev && base <= prev_last)) return TSX_REC_OFFSETS;
+    *last_out = base + (int64_t)last_delta;
+    if (count < 0) return TSX_REC_RECORDS;
+    if (comp) return 0;                                                 // a compressed batch's records cannot be read
+    return rec_frames_records(v, pos + TSX_REC_HEADER, end, count, last_delta, L, lane);
 }
 
 // The serial walk from `start` (a batch boundary, start <= stop <= avail) over every batch that begins below `stop`; the whole wave
@@ -136,11 +268,16 @@ __device__ static inline void rec_lds_init(const tsx_crc_tables* __restrict__ ta
 // header bytes, or whose end, lie behind the call's end cannot be judged here: the walk ends at it (TSX_REC_WALK_PENDING, w->exit) and the
 // resolver carries it into the next call.  The next header's bytes are asked for before the CRC of this batch runs: the load's latency
 // passes under it - when the call holds all 61 of them.
+// FRAMES (TSX_VALIDATE_FRAMES): a batch whose CRC has passed is then examined by rec_frames_batch, and counts only if that passes too.  f:
+// the walk's further results; have_prev, prev_last: the last offset of the valid batch in front of `start`, when the caller knows it (the
+// resolver does; a walker does not, and leaves the seam to the resolver: f->has_first, f->first_base).
+template <bool FRAMES, class LDS>
 __device__ static inline void rec_walk(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, uint64_t start, uint64_t stop,
-                                       tsx_rec_lds* L, uint32_t lane, tsx_rec_walk* w) {
+                                       LDS* L, uint32_t lane, tsx_rec_walk* w, tsx_rec_walk_frames* f = nullptr, bool have_prev = false, int64_t prev_last = 0) {
     tsx_rec_cursor cur, ccur;                                           // the lanes' own (header bytes) and the wave's (CRC spans)
     rec_cursor_reset(cur); rec_cursor_reset(ccur);
     w->found = TSX_REC_WALK_FOUND; w->entry = start; w->batches = 0; w->compressed = 0; w->bad_reason = 0; w->bad_pos = 0;
+    if (FRAMES) { f->records = 0; f->first_base = 0; f->last = 0; f->has_first = 0; f->pad_ = 0; }
     uint64_t pos = start;
     bool have = false;
     uint8_t nb = 0;
@@ -166,6 +303,17 @@ __device__ static inline void rec_walk(const tsx_crc_tables* __restrict__ tab, c
                 if (end > v.avail) { w->found |= TSX_REC_WALK_PENDING; break; }
                 if (end < stop && v.avail - end >= TSX_REC_HEADER) { if (lane < TSX_REC_HEADER) nb = rec_byte(v, cur, end + lane); have = true; }
                 if (rec_crc(tab, v, ccur, pos + 21, end, L->tab, lane) != want) why = TSX_REC_CRC;
+                else if (FRAMES) {
+                    int64_t base, last;
+                    int32_t count;
+                    why = rec_frames_batch(v, pos, end, comp != 0, have_prev, prev_last, L, lane, &base, &last, &count);
+                    if (!f->has_first) { f->has_first = 1; f->first_base = base; }
+                    if (!why) {
+                        w->batches++; w->compressed += comp; pos = end;
+                        if (!comp) f->records += (uint32_t)count;
+                        have_prev = true; prev_last = last; f->last = last;
+                    }
+                }
                 else { w->batches++; w->compressed += comp; pos = end; }
             }
         }
@@ -178,8 +326,9 @@ __device__ static inline void rec_walk(const tsx_crc_tables* __restrict__ tab, c
 // (magic 2, a length that is at least a header's, ends inside the call - a candidate whose end lies behind it cannot be confirmed and is
 // skipped - and is no longer than TSX_REC_SCAN_MAX_LEN or the chunk, attribute bits 7..15 zero) AND whose CRC confirms.  Returns false when there is none among the first TSX_REC_SCAN_TRIES that look like
 // one: a chunk wholly inside a batch, a batch longer than the bound, or a hostile chunk - the resolver walks such a chunk itself.
+template <class LDS>
 __device__ static inline bool rec_find_entry(const tsx_crc_tables* __restrict__ tab, const tsx_rec_view& v, uint64_t lo, uint64_t hi,
-                                             tsx_rec_lds* L, uint32_t lane, uint64_t* entry) {
+                                             LDS* L, uint32_t lane, uint64_t* entry) {
     tsx_rec_cursor cur, ccur;
     rec_cursor_reset(cur); rec_cursor_reset(ccur);
     uint32_t tries = 0;

@@ -515,6 +515,9 @@ extern "C" int tsx_records_begin(tsx_records_state* st, uint64_t stream_bytes) {
 extern "C" int tsx_transform_batch_stream(tsx_ctx* ctx, const tsx_batch_params* params, tsx_chunk_desc* descs, uint32_t n, const void* src,
                                           size_t src_size, void* dst, size_t dst_size, int mem_kind, tsx_records_state* st) {
     if (!st) return TSX_E_INVAL;
+    // the records of a batch that is open across two calls cannot be walked without keeping the batch: not built.  Refused before a
+    // context, the state or a descriptor is looked at.
+    if (params && (params->flags & TSX_VALIDATE_FRAMES)) return TSX_E_UNSUPPORTED;
     tsx_rec_stream s;
     memcpy(&s, st, sizeof s);
     if (!tsx_records_state_ok(&s)) return TSX_E_INVAL;

@@ -754,14 +754,16 @@ int run_batch(tsx_ctx* c, const tsx_batch_params* params, tsx_chunk_desc* descs,
     const bool packed = mem_kind == TSX_MEM_HOST_PACKED;
     if (packed && mode != 0) return TSX_E_INVAL;
     uint32_t flags = mode == 2 ? TSX_CRC : params->flags;
-    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC | TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM | TSX_VALIDATE_RECORDS)) return TSX_E_INVAL;
+    if (flags & ~(TSX_COMPRESS | TSX_ENCRYPT | TSX_CRC | TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM | TSX_VALIDATE_RECORDS | TSX_VALIDATE_FRAMES)) return TSX_E_INVAL;
     // the content checksum is the compressor's to write; a decoder verifies whatever frame declares one, asked or not.  Verify on upload
     // reads back what the compressor wrote: both modify TSX_COMPRESS on transform and mean nothing anywhere else
     if (mode == 0 && (flags & (TSX_ZSTD_CHECKSUM | TSX_VERIFY)) && !(flags & TSX_COMPRESS)) return TSX_E_INVAL;
     // ... and the GCM verifier reads back what the GCM stage wrote: a modifier of TSX_ENCRYPT on transform
     if (mode == 0 && (flags & TSX_VERIFY_GCM) && !(flags & TSX_ENCRYPT)) return TSX_E_INVAL;
     // ... and the record-batch validator reads the source of an upload: a modifier of any transform
-    if (mode != 0) flags &= ~(TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM | TSX_VALIDATE_RECORDS);
+    // ... and the walk over a batch's records is part of that validator's visit to the batch: a modifier of TSX_VALIDATE_RECORDS
+    if (mode == 0 && (flags & TSX_VALIDATE_FRAMES) && !(flags & TSX_VALIDATE_RECORDS)) return TSX_E_INVAL;
+    if (mode != 0) flags &= ~(TSX_ZSTD_CHECKSUM | TSX_VERIFY | TSX_VERIFY_GCM | TSX_VALIDATE_RECORDS | TSX_VALIDATE_FRAMES);
     if (mode != 2) {
         if (params->aad_len > 64) return TSX_E_INVAL;
         if ((flags & TSX_COMPRESS) && !(params->zstd_level >= 0 && params->zstd_level <= 3)) return TSX_E_UNSUPPORTED;   // 0 = 3 (the library default), 1, 2, 3

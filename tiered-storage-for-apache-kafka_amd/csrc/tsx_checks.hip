@@ -295,15 +295,16 @@ int records_validate(tsx_run& r, hipEvent_t staged, int32_t* code) {
         o.repaired_chunks = rs->repaired; o.ms = 0;
         return TSX_OK;
     }
-    const int rc = check_block(c, tsx_records_block_bytes(r.n));
+    const bool frames = (r.flags & TSX_VALIDATE_FRAMES) != 0;           // (never on a stream: the entry point refuses it)
+    const int rc = check_block(c, tsx_records_block_bytes(r.n, frames));
     if (rc) return rs ? rc : said_per_chunk(rc);
     // the view: position 0 is the first carried header byte - stream position `origin`
     const uint32_t hdr_n = rs ? rs->hdr_n : 0;
     const uint64_t origin = rs ? rs->consumed - hdr_n : 0;
     const uint64_t total = rs ? rs->total - origin : bytes;
     const uint64_t start = rs && rs->open ? rs->open_end - origin : 0;
-    tsx_records_block_fill(c->h_check, r.descs, r.n, hdr_n);
-    const tsx_rec_block b = tsx_records_block_at(c->h_check, r.n);
+    tsx_records_block_fill(c->h_check, r.descs, r.n, hdr_n, frames);
+    const tsx_rec_block b = tsx_records_block_at(c->h_check, r.n, frames);
     if (rs) {
         tsx_rec_carry& in = b.head->in;
         in.open = rs->open; in.want = rs->want; in.reg = rs->reg; in.comp = rs->comp; in.hdr_n = hdr_n;
@@ -311,7 +312,7 @@ int records_validate(tsx_run& r, hipEvent_t staged, int32_t* code) {
     }
     if (staged) HIPCHK(hipStreamWaitEvent(c->st, staged, 0));
     float ms = 0;
-    const int wrc = timed_wait(c, &ms, [&] { tsx_launch_records(c->st, c->dev->d_crc, r.d_src, c->hd_check, r.n, total, start); });
+    const int wrc = timed_wait(c, &ms, [&] { tsx_launch_records(c->st, c->dev->d_crc, r.d_src, c->hd_check, r.n, total, start, frames); });
     if (wrc) return wrc;
     HIPCHK(hipGetLastError());
     if (!__atomic_load_n(&b.head->done, __ATOMIC_ACQUIRE)) return cannot;
@@ -336,6 +337,7 @@ int records_validate(tsx_run& r, hipEvent_t staged, int32_t* code) {
     } else {
         o.batches = h.batches; o.compressed_batches = h.compressed; o.first_bad_pos = h.first_bad_pos;
         o.first_bad_reason = h.first_bad_reason; o.repaired_chunks = h.repaired;
+        o.records = frames && h.records <= 0xFFFFFFFFull ? (uint32_t)h.records : frames ? 0xFFFFFFFFu : 0u;
     }
     o.ms = ms;
     return TSX_OK;

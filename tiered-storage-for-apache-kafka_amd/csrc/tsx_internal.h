@@ -217,6 +217,8 @@ void tsx_launch_gcm_verify(hipStream_t st, const tsx_aes_tables* d_aes, const ts
 #define TSX_REC_LENGTH    2u   /* batchLength < 49 (as a signed value) */
 #define TSX_REC_MAGIC     3u
 #define TSX_REC_CRC       4u
+#define TSX_REC_RECORDS   5u   /* TSX_VALIDATE_FRAMES: recordsCount < 0, or the records of an uncompressed batch are not recordsCount well-framed records that fill it */
+#define TSX_REC_OFFSETS   6u   /* TSX_VALIDATE_FRAMES: baseOffset / lastOffsetDelta negative or overflowing, a batch not behind its predecessor, a record's offsetDelta out of order */
 
 #define TSX_REC_WALK_FOUND   1u /* tsx_rec_walk.found: the walk had an entry */
 #define TSX_REC_WALK_PENDING 2u /* ... and ended at a batch (exit) whose header or end lies behind the call's end: the chain ends there */
@@ -225,6 +227,13 @@ struct tsx_rec_walk {            // what one walker (or the resolver in its plac
     uint64_t bad_pos;            // bad_reason != 0: the first invalid batch (the walk ended there)
     uint32_t found;              // 0: no entry (the chunk lies inside one batch, or is empty); else TSX_REC_WALK_*
     uint32_t batches, compressed, bad_reason;
+};
+// ... and with TSX_VALIDATE_FRAMES: the same, and what the resolver needs to check the order of offsets across the seam between two walkers
+struct tsx_rec_walk_frames {
+    tsx_rec_walk w;
+    uint64_t records;            // sum of recordsCount over the walker's valid uncompressed batches: the records it has read
+    int64_t first_base, last;    // has_first: baseOffset of the batch at `entry` (it has passed its CRC); w.batches != 0: baseOffset + lastOffsetDelta of the last valid batch
+    uint32_t has_first, pad_;
 };
 // What a stream carries over a call boundary (tsx_transform_batch_stream), in the VIEW's positions - position 0 is the first carried
 // header byte, or the call's first byte when none is carried.  At most one of the two is in use: hdr_n raw bytes of a header whose 61
@@ -238,7 +247,8 @@ struct tsx_rec_carry {
 struct tsx_rec_head {            // the resolver's result; `in` is the host's
     uint64_t batches, compressed, first_bad_pos;
     uint32_t first_bad_reason, repaired, done, bad_open;       // bad_open: the invalid batch is the one that was open on entry (first_bad_pos: 0)
-    uint64_t pad_[3];
+    uint64_t records;            // TSX_VALIDATE_FRAMES: records read in the valid uncompressed batches in front of the first invalid one (else 0)
+    uint64_t pad_[2];
     tsx_rec_carry in, out;
 };
 // One block of PINNED memory per validating batch holds everything the two kernels read and write besides the source bytes - the
@@ -246,15 +256,19 @@ struct tsx_rec_head {            // the resolver's result; `in` is the host's
 // small is copied (a blit kernel waits behind a chip full of compressor waves), and the walkers' 40 bytes per chunk cross PCIe once each
 // way.  The view has one chunk more than the call: chunk 0 is the carried header bytes (head->in.hdr, empty in a call that carries
 // none), chunk k + 1 is the call's chunk k.
-struct tsx_rec_block { tsx_rec_head* head; uint64_t* pos; uint64_t* off; tsx_rec_walk* walks; int32_t* verdicts; };
-size_t tsx_records_block_bytes(uint32_t n);
-tsx_rec_block tsx_records_block_at(void* base, uint32_t n);
+// frames (TSX_VALIDATE_FRAMES): the walkers' results are tsx_rec_walk_frames (fwalks; walks is nullptr) - without it the layout is what
+// it has always been.
+struct tsx_rec_block { tsx_rec_head* head; uint64_t* pos; uint64_t* off; tsx_rec_walk* walks; int32_t* verdicts; tsx_rec_walk_frames* fwalks; };
+size_t tsx_records_block_bytes(uint32_t n, bool frames = false);
+tsx_rec_block tsx_records_block_at(void* base, uint32_t n, bool frames = false);
 // Host: lays the block out for descs[0 .. n) behind hdr_n carried bytes - positions, offsets, every verdict "not looked at"
 // (TSX_E_NOMEM), head cleared.  n: the call's chunks (the view's n + 1 are the block's business).
-void tsx_records_block_fill(void* h_base, const tsx_chunk_desc* descs, uint32_t n, uint32_t hdr_n);
+void tsx_records_block_fill(void* h_base, const tsx_chunk_desc* descs, uint32_t n, uint32_t hdr_n, bool frames = false);
 // records_walk_kernel (one wave per chunk of the view) and records_resolve_kernel (one wave) on st; hd_base: the block as the device
 // addresses it; total: the stream's declared length and start: where the walk begins (the open batch's end, else 0), as view positions.
-void tsx_launch_records(hipStream_t st, const tsx_crc_tables* d_tab, const uint8_t* src, void* hd_base, uint32_t n, uint64_t total, uint64_t start);
+// frames: records_walk_frames_kernel and records_resolve_frames_kernel in their place, on a block laid out for them.
+void tsx_launch_records(hipStream_t st, const tsx_crc_tables* d_tab, const uint8_t* src, void* hd_base, uint32_t n, uint64_t total, uint64_t start,
+                        bool frames = false);
 
 // A stream's state between two calls, as the host works on it (include/tsxform.h: tsx_records_state is these 192 bytes, no pointers).
 // Positions are the STREAM's.

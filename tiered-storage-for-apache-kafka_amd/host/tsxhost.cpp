@@ -480,10 +480,18 @@ GpuTransformChunkEnumeration::GpuTransformChunkEnumeration(std::shared_ptr<Backe
 GpuTransformChunkEnumeration::GpuTransformChunkEnumeration(std::shared_ptr<Backend> be, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                                            std::optional<DataKeyAndAAD> enc, IvSupplier iv, int batchChunks, bool withCrc, uint32_t profile, bool readAhead,
                                                            int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify, bool recordsValidate, int64_t recordsStreamBytes)
+    : GpuTransformChunkEnumeration(std::move(be), std::move(inner), compress, std::move(enc), std::move(iv), batchChunks, withCrc, profile, readAhead, zstdLevel, zstdChecksum,
+                                   zstdVerify, gcmVerify, recordsValidate, recordsStreamBytes, false) {}
+GpuTransformChunkEnumeration::GpuTransformChunkEnumeration(std::shared_ptr<Backend> be, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
+                                                           std::optional<DataKeyAndAAD> enc, IvSupplier iv, int batchChunks, bool withCrc, uint32_t profile, bool readAhead,
+                                                           int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify, bool recordsValidate, int64_t recordsStreamBytes,
+                                                           bool recordsFrames)
     : be_(std::move(be)), inner_(std::move(inner)), compress_(compress), enc_(std::move(enc)), iv_(std::move(iv)), batch_(batchChunks), withCrc_(withCrc),
       profile_(profile), readAhead_(readAhead), level_(zstdLevel), checksum_(zstdChecksum), verify_(zstdVerify), gcmVerify_(gcmVerify),
-      recordsValidate_(recordsValidate), recordsStreamBytes_(recordsStreamBytes) {
+      recordsValidate_(recordsValidate), recordsStreamBytes_(recordsStreamBytes), recordsFrames_(recordsFrames) {
     if (!inner_) throw std::invalid_argument("inner cannot be null");
+    if (recordsFrames_ && (!recordsValidate_ || recordsStreamBytes_ >= 0))
+        throw std::invalid_argument("segment.records.validate.frames needs segment.records.validate, and not the streamed form");
     if (recordsStreamBytes_ < -1) throw std::invalid_argument("recordsStreamBytes must be -1 (off) or the segment's size, " + std::to_string(recordsStreamBytes_) + " given");
     if (recordsValidate_ && recordsStreamBytes_ >= 0)
         throw std::invalid_argument("segment.records.validate in one batch and streamed (recordsStreamBytes " + std::to_string(recordsStreamBytes_) + ") exclude each other");
@@ -541,7 +549,8 @@ GpuTransformChunkEnumeration::Batch GpuTransformChunkEnumeration::transformNextB
         throw std::logic_error("segment.records.validate: the whole segment must fit one batch (batchChunks x chunk size = " + std::to_string(batch_) + " x " +
                                std::to_string(inner_->originalChunkSize()) + " bytes); it is not validated in part");
     const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u) |
-                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u) | (recordsStreamBytes_ >= 0 ? TSX_VALIDATE_RECORDS : 0u);
+                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u) | (recordsStreamBytes_ >= 0 ? TSX_VALIDATE_RECORDS : 0u) |
+                           (recordsFrames_ ? TSX_VALIDATE_FRAMES : 0u);
     if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !withCrc_ && !(flags & TSX_VALIDATE_RECORDS)) { out.chunks = std::move(in); return out; }     // pure base: nothing to do
     std::vector<tsx_chunk_desc> d(in.size());
     size_t so = 0, dofs = 0;
@@ -583,7 +592,8 @@ GpuTransformChunkEnumeration::PackedBatch GpuTransformChunkEnumeration::transfor
         throw std::logic_error("segment.records.validate: the whole segment must fit one batch (batchChunks x chunk size = " + std::to_string(batch_) + " x " +
                                std::to_string(inner_->originalChunkSize()) + " bytes); it is not validated in part");
     const uint32_t flags = (compress_ ? TSX_COMPRESS : 0u) | (enc_ ? TSX_ENCRYPT : 0u) | (withCrc_ ? TSX_CRC : 0u) | (checksum_ ? TSX_ZSTD_CHECKSUM : 0u) | (verify_ ? TSX_VERIFY : 0u) | (gcmVerify_ ? TSX_VERIFY_GCM : 0u) |
-                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u) | (recordsStreamBytes_ >= 0 ? TSX_VALIDATE_RECORDS : 0u);
+                           (recordsValidate_ ? TSX_VALIDATE_RECORDS : 0u) | (recordsStreamBytes_ >= 0 ? TSX_VALIDATE_RECORDS : 0u) |
+                           (recordsFrames_ ? TSX_VALIDATE_FRAMES : 0u);
     if ((flags & (TSX_COMPRESS | TSX_ENCRYPT)) == 0 && !(flags & TSX_VALIDATE_RECORDS)) {      // pure base: the chunks are the object
         for (const Bytes& c : in) {
             out.object.insert(out.object.end(), c.begin(), c.end());

@@ -261,6 +261,14 @@ public:
     GpuTransformChunkEnumeration(std::shared_ptr<Backend> backend, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
                                  std::optional<DataKeyAndAAD> encryption, IvSupplier ivSupplier, int batchChunks, bool withCrc, uint32_t zstdProfile, bool readAhead,
                                  int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify, bool recordsValidate, int64_t recordsStreamBytes);
+    // recordsFrames (segment.records.validate.frames, TSX_VALIDATE_FRAMES; false in the constructors above): with recordsValidate, every
+    // record batch that has passed its CRC is examined further on the device - the order of base offsets from batch to batch, the record
+    // count, and for an uncompressed batch the varint framing and the offset deltas of every record.  Without recordsValidate, or
+    // together with the streamed form (recordsStreamBytes >= 0): std::invalid_argument.
+    GpuTransformChunkEnumeration(std::shared_ptr<Backend> backend, std::shared_ptr<TransformChunkEnumeration> inner, bool compress,
+                                 std::optional<DataKeyAndAAD> encryption, IvSupplier ivSupplier, int batchChunks, bool withCrc, uint32_t zstdProfile, bool readAhead,
+                                 int zstdLevel, bool zstdChecksum, bool zstdVerify, bool gcmVerify, bool recordsValidate, int64_t recordsStreamBytes,
+                                 bool recordsFrames);
     ~GpuTransformChunkEnumeration() override;
     // Zstandard level of the frames (compression.zstd.level): 0 = the library default (3, what the reference uses), 1, 2 or 3;
     // anything else is refused here, not at the first batch
@@ -287,6 +295,7 @@ public:
     // and reason behind TSX_E_RECORDS' text; when `inner` is exhausted the stream must be complete - a segment that ended at another
     // length than declared has not been validated and raises std::logic_error naming both numbers.
     int64_t recordsStreamBytes() const { return recordsStreamBytes_; }
+    bool recordsFrames() const { return recordsFrames_; }
     int originalChunkSize() const override { return inner_->originalChunkSize(); }
     std::optional<int> transformedChunkSize() const override { return transformedChunkSize_; }
     bool hasMoreElements() override;
@@ -321,6 +330,7 @@ private:
     bool gcmVerify_;
     bool recordsValidate_;
     int64_t recordsStreamBytes_;
+    bool recordsFrames_;
     tsx_records_state recordsState_;                   // the stream between two batches (recordsStreamBytes_ >= 0)
     uint64_t recordsConsumed_ = 0;
     void runBatch(const tsx_batch_params& p, std::vector<tsx_chunk_desc>& d, const uint8_t* src, size_t srcSize, uint8_t* dst, size_t dstSize, bool packed);
@@ -379,6 +389,7 @@ public:
     bool zstdVerify() const { return inner_->zstdVerify(); }
     bool gcmVerify() const { return inner_->gcmVerify(); }
     bool recordsValidate() const { return inner_->recordsValidate(); }
+    bool recordsFrames() const { return inner_->recordsFrames(); }
     int64_t recordsStreamBytes() const { return inner_->recordsStreamBytes(); }     // (the finisher holds no options of its own: it transforms through its enumeration)
 
 private:

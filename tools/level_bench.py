@@ -22,13 +22,17 @@ per segment) against the one 256-chunk call: off / streamed / one call / off in 
 the flag (a caller issues its calls one after another: what batches of 64 cost by themselves).  The rows carry GiB/s, the validator's time
 summed over the segment's calls (records_ms; records_ms_calls: per call of the last segment) and the pinned source a broker's upload thread
 would hold for such a batch (pinned_source_bytes: gpuBatchChunks x chunk size).  Default --out: profiles/records_stream_level_bench.jsonl.
+--records-frames: the same segment, 5 callers, TSX_VALIDATE_RECORDS alone / with TSX_VALIDATE_FRAMES / with it / alone in one process (the
+64 generated pieces repeat four times: every repetition's base offsets are moved up, which needs no new CRC, so that the order of offsets
+holds over the whole stream).  Per run the GiB/s, tsx_records_info.ms and the records read.  Default --out:
+profiles/records_frames_level_bench.jsonl.
 --device-profile: TSX_ZSTD_PROFILE_DEVICE (standard frames from the lane-parallel parse, no library's bytes) against the exact level 3 of
 profile 1.5.7 in the same process: 1.5.7 / device / device / 1.5.7 per content.  Two regimes: the `value` shape (the defaults: 5 callers,
 8 x 1 GiB) and a lone segment (--callers 1 --segments 1: one 256-chunk batch at a time).  Every row carries GiB/s, frames / original and
 the service's kernel time; the exact rows' sample is compared with libzstd's frames, the device rows' sample is opened with the oracle's
 GCM and DECODED by libzstd.  Default --out: profiles/device_profile_level_bench.jsonl.
   python tools/level_bench.py [--steps 20] [--warmup 5] [--callers 5] [--rounds 2] [--contents K,B] [--segments 8] [--levels 3] [--checksum] [--verify]
-                              [--verify-gcm] [--records] [--records-stream] [--device-profile] [--out FILE]"""
+                              [--verify-gcm] [--records] [--records-stream] [--records-frames] [--device-profile] [--out FILE]"""
 import argparse
 import ctypes
 import json
@@ -71,7 +75,14 @@ def records_bench(args, emit):
     t_gen = time.perf_counter()
     with ProcessPoolExecutor(16, mp_context=mp.get_context("spawn")) as ex:
         pieces = list(ex.map(_gen_b_stream_piece, [(1000, 0, c, CH) for c in range(64)]))
-    stream = np.concatenate([pieces[i % 64] for i in range(256)])
+    parts = [pieces[i % 64] for i in range(256)]
+    if args.records_frames:
+        for i in range(64, 256):
+            c = parts[i].copy()
+            for p_, l_ in synth.record_batches_of(c):
+                c[p_:p_ + 8] = np.frombuffer((int.from_bytes(bytes(c[p_:p_ + 8]), "big") + ((i // 64) << 40)).to_bytes(8, "big"), np.uint8)
+            parts[i] = c
+    stream = np.concatenate(parts)
     total = int(stream.size)
     n = (total + CH - 1) // CH
     gen_s = time.perf_counter() - t_gen
@@ -93,10 +104,12 @@ def records_bench(args, emit):
     PER = 64                                                            # chunks per call of a streamed segment
     last_ms = [[] for _ in range(T)]
     # (the fifth run of --records-stream: the same four calls per segment without the flag - what the smaller batches cost by themselves)
-    for mode in (("off", "streamed", "one call", "off", "off, four calls") if args.records_stream else ("off", "one call", "one call", "off")):
+    for mode in (("off", "streamed", "one call", "off", "off, four calls") if args.records_stream else
+                 ("one call", "one call, frames", "one call, frames", "one call") if args.records_frames else ("off", "one call", "one call", "off")):
         on = not mode.startswith("off")
+        frames = mode.endswith("frames")
         cut = mode in ("streamed", "off, four calls")
-        p = nat.Native.make_params(flags | (nat.VALIDATE_RECORDS if on else 0), synth.KEY, synth.AAD, zstd_level=3)
+        p = nat.Native.make_params(flags | (nat.VALIDATE_RECORDS if on else 0) | (nat.VALIDATE_FRAMES if frames else 0), synth.KEY, synth.AAD, zstd_level=3)
         ds = [d.copy() for _ in range(T)]
 
         def step(t):
@@ -135,6 +148,7 @@ def records_bench(args, emit):
                "pinned_source_bytes": (PER if cut else n) * CH, "gibs": round(args.steps * total / GiB / el, 3), "elapsed_s": round(el, 3), "chunks": n, "stream_bytes": total,
                "steps": args.steps, "callers": T, "all_ok": bool(ok), "records_ms": round(sum(last_ms[0]) if mode == "streamed" else r.ms, 3),
                "records_ms_calls": [round(x, 3) for x in last_ms[0]] if mode == "streamed" else None, "repaired_chunks": r.repaired_chunks, "batches": r.batches,
+               "frames": frames, "records_read": r.records, "first_bad_reason": r.first_bad_reason,
                "first_bad_pos": None if r.first_bad_pos == 0xFFFFFFFFFFFFFFFF else r.first_bad_pos, "crc_ms": round(crc_ms, 3), "generated_in_s": round(gen_s, 1)}
         rows.append(row)
         emit(row)
@@ -157,6 +171,7 @@ def main():
     ap.add_argument("--verify-gcm", action="store_true", help="each level without and with TSX_VERIFY_GCM, alternating")
     ap.add_argument("--records", action="store_true", help="TSX_VALIDATE_RECORDS off / on / on / off on one valid segment of content B")
     ap.add_argument("--records-stream", action="store_true", help="the same segment: off / streamed in four calls of 64 chunks / one 256-chunk call / off")
+    ap.add_argument("--records-frames", action="store_true", help="the same segment: TSX_VALIDATE_RECORDS alone / with TSX_VALIDATE_FRAMES / with it / alone")
     ap.add_argument("--device-profile", action="store_true", help="profile 1.5.7 level 3 / device / device / 1.5.7 in one process")
     ap.add_argument("--out", default=None, help="append every JSON line to this file as well")
     args = ap.parse_args()
@@ -164,6 +179,8 @@ def main():
         args.out = os.path.join(ROOT, "profiles", "device_profile_level_bench.jsonl")
     if args.records_stream and not args.out:
         args.out = os.path.join(ROOT, "profiles", "records_stream_level_bench.jsonl")
+    if args.records_frames and not args.out:
+        args.out = os.path.join(ROOT, "profiles", "records_frames_level_bench.jsonl")
     if args.records and not args.out:
         args.out = os.path.join(ROOT, "profiles", "records_level_bench.jsonl")
     if args.verify_gcm and not args.out:
@@ -176,7 +193,7 @@ def main():
             with open(args.out, "a") as f:
                 f.write(line + "\n")
 
-    if args.records or args.records_stream:
+    if args.records or args.records_stream or args.records_frames:
         return records_bench(args, emit)
     import torch  # before libtsxform: one shared HIP runtime
     import tsxform
